@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark of the ORV denoising hot path on MI355X (contract: see the task brief / DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" is ONE denoise step of BASELINE.json configs[1] - CogVideoX-2B (ORV "1.7b": D=1920, 30 heads x 64, 30 layers,
 FFN 7680) on 320x480x17-frame clips = latents [B,5,32,40,60] (16 noisy + 16 image-condition channels), 226 text tokens +
@@ -11,9 +11,12 @@ Inputs are synthetic (seed 42), weights random N(0, 0.02^2) of t
 before the timed region.  N > 1 = N independent replicas (inference has no collective, evaluation_control_to_video.py:212-222);
 value = N*B*K / max-over-ranks(wall).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel: algorithmic FLOPs / live HIP-event duration vs the
-2.5 PFLOP/s dense bf16 MFMA peak) and, at N=1, `cpu_baseline` (the CPU oracle timed on the host cores - a reported
-baseline, not the target).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, per-step statistics); `--dump-outputs DIR` also writes what the last timed step returned as DIR/<name>.npy.
+`--full` adds everything that takes runs of its own: the per-kernel timeline of a second, eager loop and `roofline`
+(dominant kernel: algorithmic FLOPs / live HIP-event duration vs the 2.5 PFLOP/s dense bf16 MFMA peak, live rocprofv3 PMC
+passes), the VAE-decode leg, the b1 / attention / cond / train legs and, at N=1, `cpu_baseline` (the CPU oracle timed on
+the host cores - a reported baseline, not the target).
 """
 from __future__ import annotations
 
@@ -59,6 +62,27 @@ def synthetic_inputs(B, dev, dtype, frames=5, h=40, w=60):
     actions = torch.randn(B, 4 * (frames - 1), 7, generator=g) * torch.tensor([20.0] * 6 + [1.0])
     actions[..., 6].clamp_(0, 1)
     return (latents.to(dev, dtype), image_latents.to(dev, dtype), prompt.to(dev, dtype), actions.to(dev))
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as float32 `out_dir/<name>.npy` (same arguments -> same inputs, so two builds compare
+    output for output)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def param_sample(model, per_param=256, seed=0):
+    """A fixed, seeded sample of the parameters (up to `per_param` elements of each, named order), concatenated: what a
+    training step hands back, at a size that can be written every run."""
+    g = torch.Generator().manual_seed(seed)
+    parts = []
+    for _, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        idx = torch.randint(0, flat.numel(), (min(per_param, flat.numel()),), generator=g).to(flat.device)
+        parts.append(flat[idx].float())
+    return torch.cat(parts)
 
 
 def build_model(cfg, dev):
@@ -156,7 +180,7 @@ def live_pmc(dom_symbol, timeout_s=420):
         return None
     out = tempfile.mkdtemp(prefix="orv_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--eager", "--no-legs", "--no-vae",
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--eager", "--full", "--no-legs", "--no-vae",
              "--no-cpu-baseline", "--no-pmc"]
     sym = lambda name: name.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0].strip()
     res = {}
@@ -294,6 +318,8 @@ def train_mode(args, model, latents, image_latents, prompt, actions, sched, dev,
         loss = step()
     barrier()
     wall = time.perf_counter() - t0
+    if leg is None and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "params_sample": param_sample(model)})
     if leg is not None:            # `train` leg of the default (denoise) line: configs[2] at B clips, N = 1, a few steps
         c_ = cfg or {**CFG_2B, "num_layers": args.layers}
         fl = 3.0 * flops_per_sample(c_, 226 + 3000)
@@ -383,18 +409,22 @@ def main():
     ap.add_argument("--layers", type=int, default=30, help="debug only; anything but 30 marks the line INVALID")
     ap.add_argument("--mode", choices=["denoise", "train"], default="denoise",
                     help="denoise (headline, BASELINE configs[1]) or train (configs[2]: one SFT step = fwd+bwd+all-reduce+AdamW)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: per-kernel timeline + roofline (live PMC), VAE decode, the legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
     ap.add_argument("--graph", action="store_true", help="(default since round 3) replay the transformer forward from a HIP graph")
     ap.add_argument("--eager", action="store_true", help="time the eager launch path instead of the HIP-graph replay")
-    ap.add_argument("--no-legs", action="store_true", help="skip the b1 / train legs reported beside the headline (N = 1 only)")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the b1 / train legs reported beside the headline (N = 1 only)")
     ap.add_argument("--cpu-baseline-layers", type=int, default=30, help="blocks of the CPU oracle that are timed (30 = the whole step)")
     ap.add_argument("--model", choices=["2b", "5b"], default="2b",
                     help="2b = the headline (BASELINE configs[1]/[2]); 5b = configs[4] (CogVideoX1.5-5B, DROID 256x384x29f, p_t=2, "
                          "RoPE, ofs) - train mode only")
     ap.add_argument("--grad-ckpt", dest="grad_ckpt", action="store_true",
                     help="train mode: gradient checkpointing (block inputs kept, activations recomputed in the backward)")
-    ap.add_argument("--no-vae", action="store_true", help="skip the VAE-decode leg (frames/s including decode)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the three live rocprofv3 --pmc passes for roofline.traffic / mfma_busy")
+    ap.add_argument("--no-vae", action="store_true", help="--full: skip the VAE-decode leg (frames/s including decode)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not run the three live rocprofv3 --pmc passes for roofline.traffic / mfma_busy")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch the ranks, rendezvous (gloo, no GPU work), print the ranks seen and exit: checks the launcher")
     args = ap.parse_args()
@@ -504,30 +534,34 @@ def main():
     step_stats = {"median_ms": round(pct(0.5), 3), "p10_ms": round(pct(0.1), 3), "p90_ms": round(pct(0.9), 3),
                   "min_ms": round(step_ms[0], 3), "max_ms": round(step_ms[-1], 3)}
     assert torch.isfinite(lat.float()).all(), "non-finite latents"
-    # per-kernel timeline: eager loop, outside the timed region (same kernels, same shapes, same stream)
-    n_tl = args.steps if not use_graph else min(args.steps, 10)
-    lat2 = latents
-    for i in range(2):
-        lat2 = eager_step(i, lat2)
-    torch.cuda.synchronize()
-    ops.start_timeline()
-    t1 = time.perf_counter()
-    for i in range(n_tl):
-        lat2 = eager_step(i, lat2)
-    torch.cuda.synchronize()
-    eager_ms = 1e3 * (time.perf_counter() - t1) / n_tl
-    timeline = ops.stop_timeline()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": lat})        # what the last timed step returned: the next latents [B,5,16,40,60]
     if world > 1:
         w = torch.tensor([wall], device=dev, dtype=torch.float64)
         dist.all_reduce(w, op=dist.ReduceOp.MAX)
         wall = float(w.item())
     seen = ranks_seen(world, dev)
-    softmax_census = model.softmax_kernel_census(rope=False)      # which softmax form the timed weights selected, layer by layer
+    timeline = {}
+    if args.full:
+        # per-kernel timeline: eager loop, outside the timed region (same kernels, same shapes, same stream)
+        n_tl = args.steps if not use_graph else min(args.steps, 10)
+        lat2 = latents
+        for i in range(2):
+            lat2 = eager_step(i, lat2)
+        torch.cuda.synchronize()
+        ops.start_timeline()
+        t1 = time.perf_counter()
+        for i in range(n_tl):
+            lat2 = eager_step(i, lat2)
+        torch.cuda.synchronize()
+        eager_ms = 1e3 * (time.perf_counter() - t1) / n_tl
+        timeline = ops.stop_timeline()
+        softmax_census = model.softmax_kernel_census(rope=False)      # which softmax form the timed weights selected, layer by layer
     vae_leg = None
-    if not args.no_vae and args.layers == 30:
+    if args.full and not args.no_vae and args.layers == 30:
         vae_leg = vae_decode_leg(lat, dev, wall, args.steps, world, B, barrier)
     legs = {}
-    if world == 1 and not args.no_legs and args.layers == 30:
+    if args.full and world == 1 and not args.no_legs and args.layers == 30:
         # b1: the demo shape (inference_control_to_video.py runs ONE clip), graph-replayed
         l1, il1, p1, a1 = synthetic_inputs(1, dev, torch.bfloat16)
         model.action_embed.forced_mask = torch.zeros(1, dtype=torch.bool)
@@ -712,28 +746,31 @@ def main():
                                    "DDIM 50-step schedule, guidance 1.0, trajectory-conditioned",
                        "batch_per_gpu": B, "num_layers": args.layers, "parallelism": f"replica x{world} (no collective)",
                        "valid": args.layers == 30},
-            "roofline": None if dom is None else {
-                "bound": "mfma", "kernel": dom["kernel"], "shapes": dom["shapes"], "achieved": dom["tflops"],
-                "peak": MFMA_PEAK_TFLOPS,
-                "unit": "TFLOP/s", "frac": round(dom["tflops"] / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                "mfma_busy": mfma_busy, "clock_ghz_under_pmc": clock, "launches": dom["launches"], "avg_ms": dom["avg_ms"]},
-            "kernels": kernels[:8],
             "timed_path": ("default __call__ path: CogVideoXImageToVideoPipelineTraj.transformer_forward -> HIP-graph replay of the transformer forward "
                            "(automatic, bit-identical to eager)") if use_graph else "eager launches (enable_hip_graph(False))",
-            "eager_ms_per_step": round(eager_ms, 3),
-            "kernel_timeline": f"HIP events on the launch stream over a separate eager loop of {n_tl} steps after the timed region",
             "lib": {"path": os.path.relpath(LIB_PATH, ROOT), "orv_version": int(lib().orv_version())},
-            "pmc_source": pmc_source,
-            "attention_softmax": {**softmax_census, "note": "random-init qk-LayerNorm (gamma 1): every layer takes the fixed-shift kernel; "
-                                  "a checkpoint layer whose bound exceeds the limit runs the online kernel (leg attn_online = all of them, "
-                                  "leg attn_mixed = trained-like gains straddling the limit)"},
-            "vae_decode": vae_leg,
-            "b1": legs.get("b1"), "attn_online": legs.get("attn_online"), "attn_mixed": legs.get("attn_mixed"), "cond": legs.get("cond"), "train": legs.get("train"),
-            "train_5b_ckpt": legs.get("train_5b_ckpt"),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            threads = max(1, (os.cpu_count() or 2) // 2)
-            line["cpu_baseline"] = cpu_baseline(CFG_2B, args.cpu_baseline_layers, threads)
+        if args.full:
+            line.update({
+                "roofline": None if dom is None else {
+                    "bound": "mfma", "kernel": dom["kernel"], "shapes": dom["shapes"], "achieved": dom["tflops"],
+                    "peak": MFMA_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": round(dom["tflops"] / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+                    "mfma_busy": mfma_busy, "clock_ghz_under_pmc": clock, "launches": dom["launches"], "avg_ms": dom["avg_ms"]},
+                "kernels": kernels[:8],
+                "eager_ms_per_step": round(eager_ms, 3),
+                "kernel_timeline": f"HIP events on the launch stream over a separate eager loop of {n_tl} steps after the timed region",
+                "pmc_source": pmc_source,
+                "attention_softmax": {**softmax_census, "note": "random-init qk-LayerNorm (gamma 1): every layer takes the fixed-shift kernel; "
+                                      "a checkpoint layer whose bound exceeds the limit runs the online kernel (leg attn_online = all of them, "
+                                      "leg attn_mixed = trained-like gains straddling the limit)"},
+                "vae_decode": vae_leg,
+                "b1": legs.get("b1"), "attn_online": legs.get("attn_online"), "attn_mixed": legs.get("attn_mixed"), "cond": legs.get("cond"), "train": legs.get("train"),
+                "train_5b_ckpt": legs.get("train_5b_ckpt"),
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                threads = max(1, (os.cpu_count() or 2) // 2)
+                line["cpu_baseline"] = cpu_baseline(CFG_2B, args.cpu_baseline_layers, threads)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -14,7 +14,7 @@ done; done
 cd /root/repo
 for r in 1 2; do for v in prevfwd base; do
   L=/root/repo/tools/bin/dv_$v/liborv_mi355.so; [ $v = base ] && L=/root/repo/orv_amd/liborv_mi355.so
-  echo -n "$v step: "; ORV_LIB=$L python bench.py --no-vae --no-cpu-baseline --no-pmc 2>/dev/null | tail -1 | python tools/bench_line_brief.py | cut -c1-130
+  echo -n "$v step: "; ORV_LIB=$L python bench.py --full --no-vae --no-cpu-baseline --no-pmc 2>/dev/null | tail -1 | python tools/bench_line_brief.py | cut -c1-130
 done; done
 } > gpurun_out/attn_fwd_ab.txt 2>&1
 cat gpurun_out/attn_fwd_ab.txt

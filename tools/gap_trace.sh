@@ -1,9 +1,10 @@
 #!/bin/bash
 # where the graph-replayed step spends time that is not kernel time: rocprofv3 kernel trace of a short headline run, gaps between
 # consecutive kernels of the timed region -> gpurun_out/gap_trace.txt
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=/root/repo/gpurun_out/prof_gap; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o gap -- python /root/repo/bench.py --no-cpu-baseline --no-legs --no-vae --steps 12 --warmup 3 > $OUT/bench_stdout.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o gap -- python "$R/bench.py" --full --no-cpu-baseline --no-legs --no-vae --steps 12 --warmup 3 > $OUT/bench_stdout.log 2>&1
 python3 - $OUT/gap_kernel_trace.csv > /root/repo/gpurun_out/gap_trace.txt <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -2,10 +2,11 @@
 # rocprofv3 kernel-trace stats of the headline bench command (copied into profiles/ by the developer).
 # usage: bash tools/profile_bench.sh <tag> [bench args...]
 TAG=${1:-r1}; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=/root/repo/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o $TAG -- python /root/repo/bench.py --no-cpu-baseline "$@" > $OUT/bench_stdout.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o $TAG -- python "$R/bench.py" --full --no-cpu-baseline "$@" > $OUT/bench_stdout.log 2>&1
 python3 - "$OUT/${TAG}_kernel_stats.csv" > $OUT/${TAG}_kernel_stats_summary.txt <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -5,7 +5,7 @@ cd /root/repo; mkdir -p gpurun_out
 {
 timeout 1200 python -m pytest tests/test_gpu_kernels.py -x -q -k "d8 or packed" 2>&1 | tail -3
 timeout 600 python -m pytest tests/test_gpu_backward.py -x -q -k "transpose or wgrad" 2>&1 | tail -2
-B="python bench.py --no-legs --no-vae --no-cpu-baseline --no-pmc --steps 20 --warmup 5"
+B="python bench.py --full --no-legs --no-vae --no-cpu-baseline --no-pmc --steps 20 --warmup 5"
 for r in 1 2; do for b in 1 2 4; do for f in 0 1; do echo -n "B=$b ORV_GEMM_D8R192=$f : "; ORV_GEMM_D8R192=$f $B --batch $b 2>/dev/null | python tools/bench_line_brief.py; done; done; done
 for r in 1 2; do
   echo -n "B=2 r192 out=0 qkv=auto : "; ORV_PACKED_OUT=0 $B --batch 2 2>/dev/null | python tools/bench_line_brief.py

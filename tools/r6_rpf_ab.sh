@@ -11,7 +11,7 @@ done; done
 cd /root/repo
 for r in 1 2 3; do for v in base rpf1 rpf2 rpf4; do
   L=/root/repo/tools/bin/dv_$v/liborv_mi355.so; [ $v = base ] && L=/root/repo/orv_amd/liborv_mi355.so
-  echo -n "$v : "; ORV_LIB=$L python bench.py --no-legs --no-vae --no-cpu-baseline --no-pmc --steps 20 --warmup 5 2>/dev/null | python tools/bench_line_brief.py
+  echo -n "$v : "; ORV_LIB=$L python bench.py --full --no-legs --no-vae --no-cpu-baseline --no-pmc --steps 20 --warmup 5 2>/dev/null | python tools/bench_line_brief.py
 done; done
 } > /root/repo/gpurun_out/r6_rpf_ab.txt 2>&1
 cat /root/repo/gpurun_out/r6_rpf_ab.txt

@@ -4,10 +4,10 @@ R=/root/repo; O=$R/gpurun_out/refresh5; rm -rf $O; mkdir -p $O
 cd $R
 python -m pytest tests -m gpu --collect-only -q 2>/dev/null | tail -1 > $O/gpu_test_count.txt
 python -m pytest tests -m "not gpu" --collect-only -q 2>/dev/null | tail -1 >> $O/gpu_test_count.txt
-python bench.py > $O/bench_line_default.json 2> $O/bench_default.err
-python bench.py --eager --no-vae --no-cpu-baseline --no-legs --no-pmc 2>/dev/null | tail -1 > $O/bench_line_eager.json
-python bench.py --batch 1 --no-vae --no-cpu-baseline --no-legs --no-pmc 2>/dev/null | tail -1 > $O/bench_line_b1.json
-python bench.py --batch 2 --no-vae --no-cpu-baseline --no-legs --no-pmc 2>/dev/null | tail -1 > $O/bench_line_b2.json
+python bench.py --full > $O/bench_line_default.json 2> $O/bench_default.err
+python bench.py --full --eager --no-vae --no-cpu-baseline --no-legs --no-pmc 2>/dev/null | tail -1 > $O/bench_line_eager.json
+python bench.py --full --batch 1 --no-vae --no-cpu-baseline --no-legs --no-pmc 2>/dev/null | tail -1 > $O/bench_line_b1.json
+python bench.py --full --batch 2 --no-vae --no-cpu-baseline --no-legs --no-pmc 2>/dev/null | tail -1 > $O/bench_line_b2.json
 python bench.py --mode train --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/train_2b_line.json
 python bench.py --mode train --no-cpu-baseline --steps 6 --warmup 2 --grad-ckpt 2>/dev/null | tail -1 > $O/train_2b_ckpt_line.json
 python bench.py --mode train --model 5b --no-cpu-baseline --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/train_5b_line.json

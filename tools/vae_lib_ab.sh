@@ -6,7 +6,7 @@ fmt='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); v
 timeout 1200 python -m pytest tests/test_gpu_vae.py tests/test_vae_naive_golden.py -m gpu -x -q 2>&1 | tail -2
 for r in 1 2 3; do for n in "$@"; do
   L=/root/repo/tools/bin/gv_$n/liborv_mi355.so; [ "$n" = base ] && L=/root/repo/orv_amd/liborv_mi355.so
-  echo -n "vae $n (tiled, untiled ms per clip): "; ORV_LIB=$L python bench.py --no-legs --no-cpu-baseline --no-pmc --steps 3 --warmup 1 2>/dev/null | python -c "$fmt"
+  echo -n "vae $n (tiled, untiled ms per clip): "; ORV_LIB=$L python bench.py --full --no-legs --no-cpu-baseline --no-pmc --steps 3 --warmup 1 2>/dev/null | python -c "$fmt"
 done; done
 } > gpurun_out/vae_lib_ab.txt 2>&1
 cat gpurun_out/vae_lib_ab.txt
