@@ -200,6 +200,28 @@ int orv_gemm_force_epoch(void);
  * bf16 operands, fp32 accumulation, bf16 C; accumulate != 0 adds to C (gradient accumulation).  M % 8 == 0, N % 192 == 0 or N % 256 == 0. */
 int orv_gemm_tn_bf16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, int accumulate, void* stream);
 
+/* -- MXFP8 inference GEMMs (opt-in: CogVideoXTransformer3DModelTraj.enable_mxfp8) ------------------------------------------------- */
+/* Format (OCP MX, e4m3fn elements): a row-major [rows, K] bf16 matrix (K % 32 == 0) is cut into blocks of 32 consecutive K elements;
+ * block j of row r is 32 e4m3fn bytes q[r, 32j .. 32j+31] plus one e8m0 scale byte s[r, j] (value 2^(s - 127)).  q is [rows, K] uint8,
+ * s [rows, K / 32] uint8, both row-major and dense.  The scale is 2^e with e the smallest integer such that amax / 2^e <= 448 (amax =
+ * the block's largest |x|), clamped to [-127, 127]; amax == 0 gives e = 0 (byte 0x7F).  Element = x / 2^e rounded to nearest-even in
+ * e4m3fn, saturated to +-448 (-0 stays -0: byte 0x80).  The input of every producer is the bf16 value, so a fused producer and "bf16,
+ * then orv_mxfp8_quantize" give identical bytes.  Weights [N, K] use the same rule along K. */
+/* q, s = MXFP8 of x [M, K] bf16 (row stride ldx elements, 16-byte aligned rows); any M, K % 32 == 0. */
+int orv_mxfp8_quantize(const void* x, long ldx, void* q, void* s, int M, int K, void* stream);
+/* C = epilogue(A . W^T + bias) with A = g->A (e4m3 [M, K], row stride g->lda bytes) scaled by a_scale [M, K / 32] and W = g->W (e4m3
+ * [N, K], row stride g->ldw bytes) scaled by w_scale [N, K / 32]; fp32 accumulation on the block-scaled MFMA (the scales enter as the
+ * MFMA's scale operands), bf16 C.  Epilogues 0, 1 and 2 and the R / gate / grp / cmap fields as orv_gemm_bf16; no Y, no packed layouts,
+ * no epilogue 3 / 4.  No split-K: every output element is one fixed accumulation over K, whatever M.  K % 128 == 0, N % 128 == 0,
+ * lda / ldw multiples of 16 (16-byte aligned rows). */
+int orv_gemm_mxfp8(const orv_gemm_t* g, const void* a_scale, const void* w_scale, void* stream);
+/* orv_layernorm_modulate with its bf16-rounded output written as MXFP8: q [batch * seq, D] (row stride D bytes), s [batch * seq, D / 32].
+ * Byte-identical to orv_layernorm_modulate followed by orv_mxfp8_quantize (the same kernel and arithmetic; quantised at the store).
+ * D % 32 == 0.  Feeds the QKV and FFN1 GEMMs of the MXFP8 mode (cogvideox_control.py:232-234, 439). */
+int orv_layernorm_modulate_mxfp8(const void* x, int ldx, orv_rowmap_t xmap, void* q, void* s, const void* gamma, const void* beta,
+                                 const float* scale, const float* shift, long mod_b, long mod_g, orv_groups_t grp, int batch, int D,
+                                 float eps, void* stream);
+
 /* -- backward (training) ------------------------------------------------------------------------------ */
 /* dst[c, r] = src[r, c] ([R, C] bf16 -> [C, ld_dst], columns [R, ld_dst) zero-filled).  Feeds the NT GEMM with the
  * K-contiguous operands of dgrad (W^T) and wgrad (dY^T, X^T): dX = dY . W, dW = dY^T . X (torch autograd of nn.Linear). */

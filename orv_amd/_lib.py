@@ -67,6 +67,10 @@ SIGNATURES = {
     "orv_gemm_tn_bf16": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p]),
     "orv_gemm_bf16": (c_int, [POINTER(Gemm), c_void_p]),
     "orv_packed_rows": (c_long, [c_long]),
+    "orv_mxfp8_quantize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "orv_gemm_mxfp8": (c_int, [POINTER(Gemm), c_void_p, c_void_p, c_void_p]),
+    "orv_layernorm_modulate_mxfp8": (c_int, [c_void_p, c_int, RowMap, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_long, c_long, Groups, c_int, c_int, c_float, c_void_p]),
     "orv_pack_rows16": (c_int, [c_void_p, c_long, c_void_p, c_int, c_int, c_void_p]),
     "orv_unpack_rows16": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p]),
     "orv_attention_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,

@@ -391,6 +391,9 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
             self.mv_blocks = nn.ModuleList([MVBlock(**blk) for _ in range(c.num_layers)])
         self.gradient_checkpointing = False
         self._ws: Dict[Any, Dict[str, torch.Tensor]] = {}
+        self._mxfp8 = False         # MXFP8 inference mode of the block GEMMs (enable_mxfp8)
+        self._mx_gen = 0            # bumped by every enable_mxfp8 call: part of GraphedTransformer's key
+        self._mx_cache = None       # per block: (weight key, quantised QKV / out / FFN1 / FFN2 weights)
         self._set_zeros()
         self._set_trainable_parameters()
 
@@ -429,6 +432,90 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
 
     def disable_gradient_checkpointing(self):
         self.gradient_checkpointing = False
+
+    # ---- MXFP8 inference mode ----
+    def enable_mxfp8(self, enabled: bool = True):
+        """Opt-in MXFP8 inference: the four GEMMs of every transformer block (QKV, out-projection, FFN1, FFN2; :232-234, 263, 439-440) run
+        on the block-scaled MFMA with MXFP8 activations and weights (include/orv_mi355.h "MXFP8").  The embeddings, modulation tables,
+        attention, qk LayerNorm, the head (norm_final / norm_out / proj_out) and the multiview blocks stay bf16.  The weights are quantised
+        here (on the first forward when the model is not yet a bf16 model on the GPU) and again whenever a block weight changes (in-place
+        edits, moves, replaced Parameters).  Inference only: a forward in training mode or with gradients raises RuntimeError.
+        ``enable_mxfp8(False)`` returns to the bf16 path bit for bit and frees the quantised weights.  Returns ``self``."""
+        self._mxfp8 = bool(enabled)
+        self._mx_gen += 1
+        self._mx_cache = None
+        if self._mxfp8 and len(self.transformer_blocks):
+            w = self.transformer_blocks[0].ff.net[2].weight
+            if w.is_cuda and w.dtype == BF16:
+                self._mxfp8_weights()
+        return self
+
+    @property
+    def mxfp8_enabled(self) -> bool:
+        return self._mxfp8
+
+    def _mxfp8_weights(self):
+        """Per block {"qkv", "out", "ff1", "ff2": (q, s)} of the MXFP8 weights.  A block is re-quantised (into the same storage) when one of
+        its weights changed since - in-place edits bump ``_version``, moves change ``data_ptr``, a replaced Parameter changes identity, fused
+        optimizer steps move the weights epoch: the rules of ``GraphedTransformer._weights_version``."""
+        blocks = self.transformer_blocks
+        if self._mx_cache is None or len(self._mx_cache) != len(blocks):
+            self._mx_cache = [None] * len(blocks)
+        out = []
+        for i, blk in enumerate(blocks):
+            at, ff = blk.attn1, blk.ff
+            ws = (at.to_q.weight, at.to_k.weight, at.to_v.weight, at.to_out[0].weight, ff.net[0].proj.weight, ff.net[2].weight)
+            key = tuple((id(w), w._version, w.data_ptr(), str(w.device)) for w in ws) + (_state.weights_epoch[0],)
+            ent = self._mx_cache[i]
+            if ent is None or ent[0] != key:
+                for w in ws:
+                    if w.shape[0] % 128 or w.shape[1] % 128:
+                        raise ValueError(f"MXFP8 mode needs block GEMM widths that are multiples of 128 (got a {tuple(w.shape)} weight)")
+                old = ent[1] if ent is not None else {}
+                new = {}
+                for name, w in (("qkv", torch.cat([x.detach() for x in ws[:3]], dim=0)), ("out", ws[3]), ("ff1", ws[4]), ("ff2", ws[5])):
+                    w = w.detach().contiguous()
+                    q, sc = old.get(name, (None, None))
+                    if q is None or q.shape != w.shape or q.device != w.device:
+                        q, sc = None, None
+                    new[name] = ops.mxfp8_quantize(w, q=q, s=sc)
+                ent = self._mx_cache[i] = (key, new)
+            out.append(ent[1])
+        return out
+
+    def _mx_block(self, blk, wq, ws, m1, m2, mb, mg, grp, B, S, Nt, rope, scale):
+        """One transformer block (:394-445) with its four GEMMs on MXFP8: LayerNorm-modulate writes the MXFP8 A operand of QKV and FFN1;
+        QKV writes the raw projection, which ``orv_qkv_prep`` normalises (+ RoPE) in place; attention writes row-major bf16 and the
+        hidden state of the FeedForward is row-major bf16, both quantised for the GEMM that follows."""
+        c = self.config
+        D, heads = self.inner_dim, c.num_attention_heads
+        M = B * S
+        x, qkv, att, hbuf, s_pad = ws["x"], ws["qkv"], ws["att"], ws["h"], ws["s_pad"]
+        at, f0, f2 = blk.attn1, blk.ff.net[0].proj, blk.ff.net[2]
+        FF = f0.weight.shape[0]
+        need = M * max(D, FF)
+        if ws.get("mx_q") is None or ws["mx_q"].numel() < need:
+            ws["mx_q"] = torch.empty(need, dtype=torch.uint8, device=x.device)
+            ws["mx_s"] = torch.empty(need // 32, dtype=torch.uint8, device=x.device)
+        aq, asc = ws["mx_q"], ws["mx_s"]
+        qd, sd = aq[:M * D].view(M, D), asc[:M * D // 32].view(M, D // 32)
+        qf, sf = aq[:M * FF].view(M, FF), asc[:M * FF // 32].view(M, FF // 32)
+        ops.layernorm_modulate_mxfp8(x, qd, sd, blk.norm1.norm.weight, blk.norm1.norm.bias, m1[..., D:2 * D], m1[..., :D], mb, mg, grp, B,
+                                     D, c.norm_eps)
+        _, bqkv = at.packed_qkv()
+        ops.gemm_mxfp8(qd, sd, *wq["qkv"], bqkv, qkv, M, 3 * D, D)
+        nq, nk = at.norm_q, at.norm_k
+        ops.qkv_prep(qkv, None, nq.weight, nq.bias, nk.weight, nk.bias, rope, B, S, heads, Nt, s_pad, at.eps, q_premul=scale * LOG2E)
+        bound = at.score_bound(scale, rope is not None)
+        ops.attention_fwd(qkv, None, att, B, S, heads, s_pad, 1.0 / LOG2E, score_bound=bound, ws=ws["attn_ws"])
+        ops.mxfp8_quantize(att, M, D, qd, sd, ldx=D)
+        ops.gemm_mxfp8(qd, sd, *wq["out"], at.to_out[0].bias, x, M, D, D, epilogue=2, R=x, ldr=D, gate=m1[..., 2 * D:], gate_b=mb,
+                       gate_g=mg, grp=grp)
+        ops.layernorm_modulate_mxfp8(x, qd, sd, blk.norm2.norm.weight, blk.norm2.norm.bias, m2[..., D:2 * D], m2[..., :D], mb, mg, grp, B,
+                                     D, c.norm_eps)
+        ops.gemm_mxfp8(qd, sd, *wq["ff1"], f0.bias, hbuf, M, FF, D, epilogue=1)
+        ops.mxfp8_quantize(hbuf, M, FF, qf, sf, ldx=FF)
+        ops.gemm_mxfp8(qf, sf, *wq["ff2"], f2.bias, x, M, D, FF, epilogue=2, R=x, ldr=D, gate=m2[..., 2 * D:], gate_b=mb, gate_g=mg, grp=grp)
 
     @property
     def dtype(self):
@@ -660,6 +747,9 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
                 attention_kwargs: Optional[Dict[str, Any]] = None, return_dict: bool = True, num_views: int = 1,
                 image_rotary_emb_view: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         c = self.config
+        if self._mxfp8 and (self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
+            raise RuntimeError("MXFP8 mode is inference-only: call model.eval() and run under torch.no_grad() (or "
+                               "requires_grad_(False)), or turn it off with enable_mxfp8(False) before training")
         if not hidden_states.is_cuda:
             raise RuntimeError("orv_amd runs on MI355X only: move the model and its inputs to the GPU (no CPU fallback)")
         if self.dtype != BF16:
@@ -880,10 +970,14 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
         prime_score_bounds([b.attn1 for b in self.transformer_blocks], scale, rope=rope is not None)
         if mv is not None:
             prime_score_bounds([b.attn1 for b in self.mv_blocks], scale, rope=rope_view is not None)
+        mxw = self._mxfp8_weights() if self._mxfp8 else None
         for i, blk in enumerate(self.transformer_blocks):
             if mv is not None:
                 self._mv_block(self.mv_blocks[i], mv, mv_mod[i], x, xn, grp0, B, S, Nt, num_views, T, rope_view)
             m1, m2 = mod[2 * i], mod[2 * i + 1]
+            if mxw is not None:
+                self._mx_block(blk, mxw[i], ws, m1, m2, mb, mg, grp, B, S, Nt, rope, scale)
+                continue
             at = blk.attn1
             ops.layernorm_modulate(x, xn, blk.norm1.norm.weight, blk.norm1.norm.bias, m1[..., D:2 * D], m1[..., :D],
                                    mb, mg, grp, B, D, c.norm_eps, out_packed=packed["qkv"])
@@ -1139,7 +1233,9 @@ class GraphedTransformer:
     def __call__(self, hidden_states, encoder_hidden_states, timestep, **kw):
         kw = dict(kw, hidden_states=hidden_states, encoder_hidden_states=encoder_hidden_states, timestep=timestep)
         leaves, desc = self._flatten(kw)
-        key = (desc, _state.weights_epoch[0], self._weights_version(), self.tr.training, _chains())
+        # MXFP8 state: a graph captured in one mode never replays in the other, nor after a re-enable (new quantised weights)
+        mx = (self.tr._mx_gen,) if getattr(self.tr, "_mxfp8", False) else None
+        key = (desc, _state.weights_epoch[0], self._weights_version(), self.tr.training, _chains(), mx)
         st = self._state.get(key)
         if st is None:                       # eager warm-up call
             st = self._state[key] = {"calls": 1}

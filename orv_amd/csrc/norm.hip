@@ -3,6 +3,7 @@
 //   orv_qkv_prep           : per-head LayerNorm(64) on q,k (+RoPE) in place, V -> V^T  (cogvideox_control.py:239-254)
 // One wave per row; 16-byte vector loads/stores; statistics in fp32 (two-pass in registers).
 #include "common.hpp"
+#include "mxfp8.hpp"
 
 namespace {
 
@@ -16,13 +17,15 @@ namespace {
 #ifndef ORV_LN_WAVES          // minimum waves per SIMD the register allocation must leave room for (A/B builds: tools/variants.sh)
 #define ORV_LN_WAVES 1
 #endif
-template <int CH, bool FULL>
+// MX: y is the e4m3 byte matrix of an MXFP8 output (row stride ldy bytes) and mxs its scales [rows, D / 32]: the bf16-rounded result is
+// quantised in registers (mxfp8.hpp), byte-identical to this kernel's bf16 output followed by orv_mxfp8_quantize.
+template <int CH, bool FULL, bool MX = false>
 __global__ __launch_bounds__(256, ORV_LN_WAVES) void ln_mod_kernel(const bf16_t* __restrict__ x, long ldx, bf16_t* __restrict__ y,
                                                      long ldy, const bf16_t* __restrict__ gamma,
                                                      const bf16_t* __restrict__ beta, const float* __restrict__ scale,
                                                      const float* __restrict__ shift, long mod_b, long mod_g, int seq,
                                                      int n_text, int per_group, int rows, int D, float eps,
-                                                     orv_rowmap_t xmap) {
+                                                     orv_rowmap_t xmap, uint8_t* __restrict__ mxs) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -105,9 +108,16 @@ __global__ __launch_bounds__(256, ORV_LN_WAVES) void ln_mod_kernel(const bf16_t*
         }
         uint4 u;
         u.x = pack2bf(o[0], o[1]); u.y = pack2bf(o[2], o[3]); u.z = pack2bf(o[4], o[5]); u.w = pack2bf(o[6], o[7]);
+        if constexpr (MX) {   // a lane quad is one 32-element block; quads past the row end hold copies of the last chunk: no store
+            uint2 qq;
+            uint32_t sb;
+            mx_quantize8(u, qq, sb);
+            if (ok[i]) mx_store8((uint8_t*)y + (long)row * ldy, mxs + (long)row * (D >> 5), c, qq, sb);
+        } else {
         // lanes past the row end hold the row's LAST chunk (clamped index: same input, same factors, same result): they store it too -
         // identical bytes to the same address - so the kernel has no divergent branch and its loads can be scheduled as one batch
         *(uint4*)(yr + c * 8) = u;
+        }
     }
 }
 
@@ -251,11 +261,12 @@ __device__ __forceinline__ void lnr_store(bf16_t* p, const uint4 u) {
     *(uint4*)p = u;
 #endif
 }
-template <int CH, bool PACKED = false>
+template <int CH, bool PACKED = false, bool MX = false>   // MX: as ln_mod_kernel's
 __global__ __launch_bounds__(256, ORV_LNR_WAVES) void ln_mod_rows_kernel(const bf16_t* __restrict__ x, long ldx, bf16_t* __restrict__ y, long ldy,
                                                              const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta,
                                                              const float* __restrict__ scale, const float* __restrict__ shift, long mod_b,
-                                                             long mod_g, int seq, int n_text, int per_group, int rows, int D, float eps, int R) {
+                                                             long mod_g, int seq, int n_text, int per_group, int rows, int D, float eps, int R,
+                                                             uint8_t* __restrict__ mxs) {
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int r0 = __builtin_amdgcn_readfirstlane(w * R);
@@ -334,7 +345,12 @@ __global__ __launch_bounds__(256, ORV_LNR_WAVES) void ln_mod_rows_kernel(const b
             for (int e = 0; e < 8; ++e) o[e] = fmaf((v[i][e] - mean) * rstd, gg[i][e], hh[i][e]);
             uint4 u;
             u.x = pack2bf(o[0], o[1]); u.y = pack2bf(o[2], o[3]); u.z = pack2bf(o[4], o[5]); u.w = pack2bf(o[6], o[7]);
-            if (PACKED) *(uint4*)(y + ((((long)(row >> 4) * (D >> 5) + (ce[i] >> 2)) << 9) + ((((ce[i] & 3) << 4) + (row & 15)) << 3))) = u;
+            if constexpr (MX) {
+                uint2 qq;
+                uint32_t sb;
+                mx_quantize8(u, qq, sb);
+                if (ok[i]) mx_store8((uint8_t*)y + (long)row * ldy, mxs + (long)row * (D >> 5), ce[i], qq, sb);
+            } else if (PACKED) *(uint4*)(y + ((((long)(row >> 4) * (D >> 5) + (ce[i] >> 2)) << 9) + ((((ce[i] & 3) << 4) + (row & 15)) << 3))) = u;
             else lnr_store(yr + ce[i] * 8, u);       // lanes past the row end re-store the last chunk's identical bytes
         }
     }
@@ -344,7 +360,7 @@ __global__ __launch_bounds__(256, ORV_LNR_WAVES) void ln_mod_rows_kernel(const b
 
 static int layernorm_modulate_impl(const void* x, int ldx, orv_rowmap_t xmap, void* y, int ldy, const void* gamma,
                                    const void* beta, const float* scale, const float* shift, long mod_b, long mod_g,
-                                   orv_groups_t grp, int batch, int D, float eps, void* stream, bool packed) {
+                                   orv_groups_t grp, int batch, int D, float eps, void* stream, bool packed, uint8_t* mxs = nullptr) {
     ORV_REQUIRE(x && y, "orv_layernorm_modulate: null operand");
     ORV_REQUIRE(D % 8 == 0 && D <= 4096, "orv_layernorm_modulate: D=%d must be a multiple of 8 and <= 4096", D);
     ORV_REQUIRE(grp.seq > 0 && batch > 0, "orv_layernorm_modulate: empty problem");
@@ -355,6 +371,8 @@ static int layernorm_modulate_impl(const void* x, int ldx, orv_rowmap_t xmap, vo
     dim3 grid((rows + 3) / 4), block(256);
     hipStream_t st = (hipStream_t)stream;
     const bool full = gamma && beta && scale && shift;
+    const bool mx = mxs != nullptr;     // MXFP8 output: the same kernel choice and arithmetic as the bf16 output, quantised at the store
+    ORV_REQUIRE(!mx || (!packed && D % 32 == 0), "orv_layernorm_modulate_mxfp8: D=%d must be a multiple of 32", D);
     // rows-per-wave form: big FULL launches without a row map; R = rows per wave so that one round of resident waves (12 per CU) covers
     // the problem.  ORV_LN_ROWS=0: the one-row kernel everywhere (A/B); ORV_LN_ROWS=n: fixed R.
     static int rows_env = -2;
@@ -369,14 +387,18 @@ static int layernorm_modulate_impl(const void* x, int ldx, orv_rowmap_t xmap, vo
         const int R = rows_env > 0 ? rows_env : max(rows >= 2048 ? 2 : 1, (rows + slots - 1) / slots);
         dim3 g2(((rows + R - 1) / R + 3) / 4);
 #define ORV_LNR_CASE(C)                                                                                                \
-        if (packed)                                                                                                    \
+        if (mx)                                                                                                        \
+            hipLaunchKernelGGL((ln_mod_rows_kernel<C, false, true>), g2, block, 0, st, (const bf16_t*)x, (long)ldx, (bf16_t*)y, (long)ldy, \
+                               (const bf16_t*)gamma, (const bf16_t*)beta, scale, shift, mod_b, mod_g, grp.seq, grp.n_text, \
+                               grp.per_group, rows, D, eps, R, mxs);                                                   \
+        else if (packed)                                                                                               \
             hipLaunchKernelGGL((ln_mod_rows_kernel<C, true>), g2, block, 0, st, (const bf16_t*)x, (long)ldx, (bf16_t*)y, (long)ldy, \
                                (const bf16_t*)gamma, (const bf16_t*)beta, scale, shift, mod_b, mod_g, grp.seq, grp.n_text, \
-                               grp.per_group, rows, D, eps, R);                                                        \
+                               grp.per_group, rows, D, eps, R, nullptr);                                               \
         else                                                                                                           \
             hipLaunchKernelGGL((ln_mod_rows_kernel<C>), g2, block, 0, st, (const bf16_t*)x, (long)ldx, (bf16_t*)y, (long)ldy, \
                                (const bf16_t*)gamma, (const bf16_t*)beta, scale, shift, mod_b, mod_g, grp.seq, grp.n_text, \
-                               grp.per_group, rows, D, eps, R)
+                               grp.per_group, rows, D, eps, R, nullptr)
         if (ch <= 1) { ORV_LNR_CASE(1); }
         else if (ch <= 2) { ORV_LNR_CASE(2); }
         else { ORV_LNR_CASE(4); }
@@ -384,14 +406,22 @@ static int layernorm_modulate_impl(const void* x, int ldx, orv_rowmap_t xmap, vo
         return orv_check_launch("orv_layernorm_modulate");
     }
 #define ORV_LN_CASE(C)                                                                                                 \
-    if (full)                                                                                                          \
+    if (mx && full)                                                                                                    \
+        hipLaunchKernelGGL((ln_mod_kernel<C, true, true>), grid, block, 0, st, (const bf16_t*)x, (long)ldx, (bf16_t*)y, (long)ldy, \
+                           (const bf16_t*)gamma, (const bf16_t*)beta, scale, shift, mod_b, mod_g, grp.seq, grp.n_text, \
+                           grp.per_group, rows, D, eps, xmap, mxs);                                                    \
+    else if (mx)                                                                                                       \
+        hipLaunchKernelGGL((ln_mod_kernel<C, false, true>), grid, block, 0, st, (const bf16_t*)x, (long)ldx, (bf16_t*)y, (long)ldy, \
+                           (const bf16_t*)gamma, (const bf16_t*)beta, scale, shift, mod_b, mod_g, grp.seq, grp.n_text, \
+                           grp.per_group, rows, D, eps, xmap, mxs);                                                    \
+    else if (full)                                                                                                     \
         hipLaunchKernelGGL((ln_mod_kernel<C, true>), grid, block, 0, st, (const bf16_t*)x, (long)ldx, (bf16_t*)y, (long)ldy, \
                            (const bf16_t*)gamma, (const bf16_t*)beta, scale, shift, mod_b, mod_g, grp.seq, grp.n_text, \
-                           grp.per_group, rows, D, eps, xmap);                                                         \
+                           grp.per_group, rows, D, eps, xmap, nullptr);                                                \
     else                                                                                                               \
         hipLaunchKernelGGL((ln_mod_kernel<C, false>), grid, block, 0, st, (const bf16_t*)x, (long)ldx, (bf16_t*)y, (long)ldy, \
                            (const bf16_t*)gamma, (const bf16_t*)beta, scale, shift, mod_b, mod_g, grp.seq, grp.n_text, \
-                           grp.per_group, rows, D, eps, xmap)
+                           grp.per_group, rows, D, eps, xmap, nullptr)
     if (ch <= 1) { ORV_LN_CASE(1); }
     else if (ch <= 2) { ORV_LN_CASE(2); }
     else if (ch <= 4) { ORV_LN_CASE(4); }
@@ -413,6 +443,14 @@ extern "C" int orv_layernorm_modulate_packed(const void* x, int ldx, void* y, co
                                              void* stream) {
     orv_rowmap_t none{0, 0, 0};
     return layernorm_modulate_impl(x, ldx, none, y, D, gamma, beta, scale, shift, mod_b, mod_g, grp, batch, D, eps, stream, true);
+}
+// q [batch * seq, D] e4m3 (row stride D bytes) + s [batch * seq, D / 32] e8m0: the MXFP8 form of orv_layernorm_modulate's bf16 output
+extern "C" int orv_layernorm_modulate_mxfp8(const void* x, int ldx, orv_rowmap_t xmap, void* q, void* s, const void* gamma, const void* beta,
+                                            const float* scale, const float* shift, long mod_b, long mod_g, orv_groups_t grp, int batch, int D,
+                                            float eps, void* stream) {
+    ORV_REQUIRE(q && s && ((uintptr_t)q & 7) == 0, "orv_layernorm_modulate_mxfp8: null or misaligned q / s");
+    return layernorm_modulate_impl(x, ldx, xmap, q, D, gamma, beta, scale, shift, mod_b, mod_g, grp, batch, D, eps, stream, false,
+                                   (uint8_t*)s);
 }
 
 extern "C" int orv_qkv_prep_from(const void* src, void* qkv, void* vT, const void* gq, const void* bq, const void* gk,

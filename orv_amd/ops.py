@@ -151,6 +151,47 @@ def layernorm_modulate(x, y, gamma, beta, scale, shift, mod_b, mod_g, grp: Group
     return y
 
 
+def layernorm_modulate_mxfp8(x, q, s, gamma, beta, scale, shift, mod_b, mod_g, grp: Groups, batch, D, eps, ldx=None,
+                             xmap: Optional[RowMap] = None):
+    """``layernorm_modulate`` with the bf16-rounded output written as MXFP8: ``q`` uint8 [batch * seq, D] (e4m3fn bytes) and ``s`` uint8
+    [batch * seq, D / 32] (e8m0 block scales); byte-identical to ``layernorm_modulate`` followed by ``mxfp8_quantize``."""
+    _need(x, BF16, "x"), _need(q, torch.uint8, "q"), _need(s, torch.uint8, "s")
+    check(lib().orv_layernorm_modulate_mxfp8(_p(x), ldx or D, xmap or RowMap(0, 0, 0), _p(q), _p(s), _p(gamma), _p(beta), _p(scale),
+                                             _p(shift), mod_b, mod_g, grp, batch, D, float(eps), _stream()),
+          "orv_layernorm_modulate_mxfp8")
+    return q, s
+
+
+def mxfp8_quantize(x, M=None, K=None, q=None, s=None, ldx=None):
+    """MXFP8 of a row-major bf16 [M, K] matrix (include/orv_mi355.h "MXFP8"): -> (q uint8 [M, K], s uint8 [M, K / 32])."""
+    _need(x, BF16, "x")
+    M = x.shape[0] if M is None else M
+    K = x.shape[-1] if K is None else K
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device) if q is None else _need(q, torch.uint8, "q")
+    s = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device) if s is None else _need(s, torch.uint8, "s")
+    check(lib().orv_mxfp8_quantize(_p(x), ldx or x.stride(0), _p(q), _p(s), M, K, _stream()), "orv_mxfp8_quantize")
+    return q, s
+
+
+def gemm_mxfp8(A, A_scale, W, W_scale, bias, C, M, N, K, epilogue=0, R=None, r_mod=0, gate=None, gate_b=0, gate_g=0,
+               grp: Optional[Groups] = None, cmap: Optional[RowMap] = None, ldc=None, ldr=None):
+    """``gemm`` on MXFP8 operands: A (uint8 [M, K]) / A_scale (uint8 [M, K / 32]) and W (uint8 [N, K]) / W_scale (uint8 [N, K / 32]) from
+    ``mxfp8_quantize`` / ``layernorm_modulate_mxfp8``; bf16 C; epilogues 0 / 1 / 2 as in ``gemm``."""
+    for t, n in ((A, "A"), (A_scale, "A_scale"), (W, "W"), (W_scale, "W_scale")):
+        _need(t, torch.uint8, n)
+    _need(C, BF16, "C")
+    g = Gemm()
+    g.A, g.lda, g.W, g.ldw, g.bias = _p(A), K, _p(W), K, _p(bias)
+    g.C, g.ldc, g.M, g.N, g.K, g.epilogue = _p(C), ldc or N, M, N, K, epilogue
+    g.R, g.ldr, g.r_mod = _p(R), ldr or N, r_mod
+    g.gate, g.gate_b, g.gate_g = _p(gate), gate_b, gate_g
+    g.grp = grp or Groups(0, 0, 0)
+    g.cmap = cmap or RowMap(0, 0, 0)
+    with _timed(("gemm_mxfp8", M, N, K, epilogue)):
+        check(lib().orv_gemm_mxfp8(g, _p(A_scale), _p(W_scale), _stream()), "orv_gemm_mxfp8")
+    return C
+
+
 def gemm_tn(A, W, C, M, N, K, accumulate=False, lda=None, ldw=None, ldc=None):
     """C[M, N] (+)= A[K, M]^T . W[K, N]  (both operands row-major over the K contraction rows: dW = dY^T X without transposes)."""
     _need(A, BF16, "A"), _need(W, BF16, "W"), _need(C, BF16, "C")
