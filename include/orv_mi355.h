@@ -272,6 +272,21 @@ int orv_adamw_flat(void* p, const void* g, float* m, float* v, long n, const lon
 int orv_adamw_flat_steps(void* p, const void* g, float* m, float* v, long n, const long* seg_start,
                          const unsigned char* seg_active, const int* seg_step, int nseg, float lr, float beta1, float beta2,
                          float eps, float weight_decay, int step, const float* clip_coef, void* stream);
+/* orv_adamw_flat_steps with an opt-in parameter precision (FusedAdamW(param_precision=...)):
+ *   mode 0 "bf16"       - exactly orv_adamw_flat_steps (the same kernel); `lo` and `seed` are ignored.
+ *   mode 1 "split_fp32" - an exact fp32 master weight in 2 extra bytes per element: `lo` (int16[n], same layout as p) holds the low
+ *                         half, master_bits = (p_bits << 16) + sign_extend(lo); the update runs on the master and writes back
+ *                         p_bits = (master_bits + 0x8000) >> 16 (nearest, ties AWAY from zero), lo = master_bits - (p_bits << 16).
+ *                         A non-finite master writes the matching non-finite bf16 (NaN quiet) and lo = 0.  `lo` is required.
+ *   mode 2 "stochastic" - the fp32 result is stored as p_bits = (bits + r) >> 16, r a uniform 16-bit integer from a counter-based
+ *                         hash of (seed, step, flat element index) only (defined in orv_amd/csrc/optim.hip): identical on every
+ *                         run and every data-parallel rank.  Non-finite results are written unperturbed; a finite result is never
+ *                         carried into infinity (largest finite bf16 instead).  `lo` is ignored.
+ * Any other mode, or mode 1 without `lo`, returns non-zero with an orv_last_error message. */
+int orv_adamw_flat_ex(void* p, const void* g, float* m, float* v, long n, const long* seg_start,
+                      const unsigned char* seg_active, const int* seg_step, int nseg, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, int step, const float* clip_coef, void* lo, int mode, unsigned seed,
+                      void* stream);
 /* dst_ptr[s][j] = bf16(src[src_off[s] + j]), j < len[s], for nseg segments (src_off / dst_ptr / len are DEVICE arrays; dst_ptr holds
  * device addresses of bf16 storage; max_len = max len[s]): the small fp32-accumulated parameter gradients go from the backward's
  * accumulator arena into the fused optimizer's flat gradient buffer in one launch (the reference leaves this to autograd's

@@ -491,6 +491,36 @@ def adamw_flat(p, g, m, v, seg_start, seg_active, lr, beta1, beta2, eps, weight_
                                      float(weight_decay), int(step), _p(clip_coef), _stream()), "orv_adamw_flat_steps")
 
 
+ADAMW_MODES = {"bf16": 0, "split_fp32": 1, "stochastic": 2}
+
+
+def adamw_flat_ex(p, g, m, v, seg_start, seg_active, lr, beta1, beta2, eps, weight_decay, step, clip_coef=None, seg_step=None, lo=None,
+                  mode=0, seed=0):
+    """``adamw_flat`` with a parameter-precision mode (``ADAMW_MODES``): 0 the plain bf16 update, 1 an exact fp32 master split into the
+    bf16 weight and the int16 buffer ``lo`` (same length as ``p``), 2 stochastic rounding of the fp32 result from a hash of
+    (``seed``, ``step``, flat index)."""
+    mode = ADAMW_MODES.get(mode, mode)
+    _need(p, BF16, "p"), _need(g, BF16, "g"), _need(m, torch.float32, "m"), _need(v, torch.float32, "v")
+    _need(seg_start, torch.int64, "seg_start"), _need(seg_active, torch.uint8, "seg_active")
+    if seg_step is not None:
+        _need(seg_step, torch.int32, "seg_step")
+    if clip_coef is not None:
+        _need(clip_coef, torch.float32, "clip_coef")
+    if lo is not None:
+        _need(lo, torch.int16, "lo")
+        if lo.numel() != p.numel():
+            raise RuntimeError(f"orv_amd.ops: `lo` holds {lo.numel()} elements, `p` {p.numel()}")
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v), ("seg_start", seg_start), ("seg_active", seg_active), ("seg_step", seg_step),
+                    ("lo", lo)):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+    if g.numel() < p.numel() or m.numel() != p.numel() or v.numel() != p.numel() or seg_start.numel() != seg_active.numel() + 1:
+        raise RuntimeError("orv_amd.ops: adamw_flat_ex buffers do not share one flat layout")
+    check(lib().orv_adamw_flat_ex(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(seg_start), _p(seg_active), _p(seg_step),
+                                  seg_active.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                  int(step), _p(clip_coef), _p(lo), int(mode), int(seed) & 0xFFFFFFFF, _stream()), "orv_adamw_flat_ex")
+
+
 def sumsq(g, out):
     check(lib().orv_sumsq(_p(g), g.numel(), _p(out), _stream()), "orv_sumsq")
 

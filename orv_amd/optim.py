@@ -11,7 +11,12 @@ in a step are skipped exactly as ``torch.optim.AdamW`` skips them (segment activ
 OWN step count for the bias correction (``state[p]["step"]`` in torch).  Under data parallel a parameter is active iff it has a gradient on ANY rank (the usage mask rides in the last segment of the flat gradient buffer, so it arrives with the gradient
 exchange itself: DDP's ``find_unused_parameters`` bookkeeping, which the reference enables, base_train.yaml:181); a rank without one contributes zeros,
 so the collective schedule and the update are identical on all ranks and equal to the single-GPU trajectory.  Moments
-are fp32 (the reference keeps them in the parameter dtype)."""
+are fp32 (the reference keeps them in the parameter dtype).
+
+Parameter precision (``param_precision``): the default ``"bf16"`` rounds every updated weight back to bf16 to nearest-even, as the
+reference's bf16 training does, so an update below half a bf16 step of the weight is lost whole.  ``"split_fp32"`` keeps an exact fp32 master
+in 2 extra bytes per element (a flat int16 buffer of low halves beside the bf16 weights the model reads), ``"stochastic"`` rounds the fp32 result
+to bf16 with a 16-bit random offset drawn from a hash of (seed, step count, flat index) - unbiased, no extra memory, identical on every rank."""
 from __future__ import annotations
 
 from typing import Iterable, List, Optional
@@ -21,13 +26,19 @@ import torch
 from . import _state, ops
 
 _SEG = 2048          # elements per workgroup of orv_adamw_flat; every segment is padded to a multiple of it
+PARAM_PRECISIONS = ("bf16", "split_fp32", "stochastic")
 _AR_CHUNK = 128 * 1024 * 1024   # bf16 elements per all-reduce call (256 MB: large enough that xGMI link bandwidth, not
 #                                 launch latency, bounds the ring)
 
 
 class FusedAdamW:
     def __init__(self, params: Iterable[torch.nn.Parameter], lr=1e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-3,
-                 max_grad_norm: float = 1.0):
+                 max_grad_norm: float = 1.0, param_precision: str = "bf16", seed: int = 0):
+        if param_precision not in PARAM_PRECISIONS:
+            raise ValueError(f"FusedAdamW: unknown param_precision {param_precision!r} (one of {', '.join(PARAM_PRECISIONS)})")
+        if not 0 <= int(seed) < 2 ** 32:
+            raise ValueError(f"FusedAdamW: seed={seed} must be a 32-bit unsigned integer")
+        self.param_precision, self.seed = param_precision, int(seed)
         ps = [p for p in params if p.requires_grad]
         # flat-buffer order: parameters the model tagged as "gradient final when its block's backward ends" first (model order: a block's
         # six weights are contiguous), everything else behind them - see CogVideoXTransformer3DModelTraj._set_trainable_parameters and
@@ -74,6 +85,11 @@ class FusedAdamW:
             seg_start=torch.tensor(offs + [total], dtype=torch.int64, device=dev),
             active=torch.zeros(len(self.params), dtype=torch.uint8, device=dev), active_host=[False] * len(self.params),
             seg_step=torch.zeros(len(self.params), dtype=torch.int32, device=dev))
+        if self.param_precision == "split_fp32":
+            # low halves of the fp32 masters, same segment layout as `p`; zeros: the master is the current bf16 value exactly
+            lo = torch.zeros(total, dtype=torch.int16, device=dev)
+            self._flat.update(lo=lo, views_lo=[lo[off:off + p.numel()] for p, off in zip(self.params, offs)])
+            self._seen_versions = [p._version for p in self.params]
         _state.register_grad_views(self.params, self)
         _state.bump_weights_epoch()      # parameter storage moved (p.data = view): captured graphs / derived-weight caches are stale
 
@@ -204,20 +220,74 @@ class FusedAdamW:
             clip = clip / world
         self.step_count += 1
         f["seg_step"].add_(f["active"].to(torch.int32))          # per-parameter step counts (torch.optim.AdamW state["step"])
-        ops.adamw_flat(f["p"], f["g"], f["m"], f["v"], f["seg_start"], f["active"], self.param_groups[0]["lr"], self.betas[0],
-                       self.betas[1], self.eps, self.weight_decay, self.step_count, clip, seg_step=f["seg_step"])
+        if self.param_precision == "bf16":
+            ops.adamw_flat(f["p"], f["g"], f["m"], f["v"], f["seg_start"], f["active"], self.param_groups[0]["lr"], self.betas[0],
+                           self.betas[1], self.eps, self.weight_decay, self.step_count, clip, seg_step=f["seg_step"])
+        else:
+            if "lo" in f:
+                self._drop_stale_param_lo()
+            ops.adamw_flat_ex(f["p"], f["g"], f["m"], f["v"], f["seg_start"], f["active"], self.param_groups[0]["lr"], self.betas[0],
+                              self.betas[1], self.eps, self.weight_decay, self.step_count, clip, seg_step=f["seg_step"],
+                              lo=f.get("lo"), mode=ops.ADAMW_MODES[self.param_precision], seed=self.seed)
         _state.bump_weights_epoch()      # parameters changed without a tensor._version bump: drop derived-weight caches
         return float(norm.item())
+
+    # ---- fp32 masters (param_precision="split_fp32") ----
+    def _drop_stale_param_lo(self):
+        """A parameter written by anything but this optimizer since the last ``step`` (``model.load_state_dict``, ``p.copy_`` under
+        ``no_grad``: both bump ``p._version``; the update kernel does not) has a low half that belongs to a weight that is gone: zero it,
+        so that the master is the new bf16 value exactly."""
+        moved = [i for i, (p, ver) in enumerate(zip(self.params, self._seen_versions)) if p._version != ver]
+        if moved:
+            torch._foreach_zero_([self._flat["views_lo"][i] for i in moved])
+            for i in moved:
+                self._seen_versions[i] = self.params[i]._version
+
+    @torch.no_grad()
+    def reset_param_lo(self, params: Optional[Iterable[torch.nn.Parameter]] = None):
+        """Zero the low halves of the fp32 masters of ``params`` (default: all), i.e. make every master equal to its current bf16 weight.
+        In-place writes to a parameter that bump ``p._version`` are seen by ``step`` and handled there; writes through ``p.data`` (or raw
+        device pointers) do NOT bump it and cannot be seen - call this after them.  A stale low half is bounded harm (the master is off by
+        at most half a bf16 step, once), never a wrong weight.  No-op outside ``param_precision="split_fp32"``."""
+        if self.param_precision != "split_fp32":
+            return
+        if self._flat is None:
+            self._build()
+        if params is None:
+            self._flat["lo"].zero_()
+        else:
+            index = {id(p): i for i, p in enumerate(self.params)}
+            for p in params:
+                if id(p) not in index:
+                    raise ValueError("FusedAdamW.reset_param_lo: a parameter this optimizer does not own")
+                self._flat["views_lo"][index[id(p)]].zero_()
+        self._seen_versions = [p._version for p in self.params]
+
+    @torch.no_grad()
+    def master_params(self) -> List[torch.Tensor]:
+        """The fp32 master of every parameter (new fp32 tensors shaped like the parameters, in ``self.params`` order): bit pattern
+        ``(p_bits << 16) + sign_extend(lo)`` under ``"split_fp32"`` (minus the low halves ``step`` would drop as stale), the bf16 value
+        itself in the other modes.  For tests and for exporting a checkpoint at full precision."""
+        if self.param_precision != "split_fp32" or self._flat is None:
+            return [p.detach().float() for p in self.params]
+        self._drop_stale_param_lo()
+        return [(p.detach().float().view(torch.int32) + lo.view(p.shape).to(torch.int32)).view(torch.float32)
+                for p, lo in zip(self.params, self._flat["views_lo"])]
 
     # ---- checkpointing (torch.optim-like) ----
     def state_dict(self):
         """Flat moments plus the layout they are stored in (parameter element counts and segment offsets), so that a resume
         with a different trainable set fails loudly instead of mis-assigning moments."""
         layout = [int(p.numel()) for p in self.params]
+        mode = {"param_precision": self.param_precision, "seed": self.seed}
         if self._flat is None:
-            return {"step": self.step_count, "exp_avg": None, "exp_avg_sq": None, "numels": layout}
-        return {"step": self.step_count, "exp_avg": self._flat["m"], "exp_avg_sq": self._flat["v"], "numels": layout,
-                "seg_start": self._flat["seg_start"].tolist(), "seg_step": self._flat["seg_step"]}
+            return {"step": self.step_count, "exp_avg": None, "exp_avg_sq": None, "numels": layout, **mode}
+        sd = {"step": self.step_count, "exp_avg": self._flat["m"], "exp_avg_sq": self._flat["v"], "numels": layout,
+              "seg_start": self._flat["seg_start"].tolist(), "seg_step": self._flat["seg_step"], **mode}
+        if "lo" in self._flat:
+            self._drop_stale_param_lo()
+            sd["param_lo"] = self._flat["lo"]
+        return sd
 
     def load_state_dict(self, sd):
         layout = [int(p.numel()) for p in self.params]
@@ -229,6 +299,21 @@ class FusedAdamW:
             raise ValueError("FusedAdamW.load_state_dict: the checkpoint was written for a different set of trainable parameters "
                              f"({len(sd['numels'])} segments vs {len(layout)} here, or different sizes)")
         self.step_count = int(sd["step"])
+        # The precision mode is the constructor's; the stored one is a record.  The seed of the stochastic sequence is taken over, so that a
+        # resumed run continues it.  Checkpoints without these keys (the default mode, older builds) load into any mode.
+        if sd.get("seed") is not None:
+            self.seed = int(sd["seed"])
+        if self.param_precision == "split_fp32" and (sd.get("param_lo") is not None or sd.get("exp_avg") is not None):
+            if self._flat is None:
+                self._build()
+            lo = sd.get("param_lo")
+            if lo is not None and lo.numel() != self._flat["lo"].numel():
+                raise ValueError(f"FusedAdamW.load_state_dict: param_lo holds {lo.numel()} elements, the flat layout {self._flat['lo'].numel()}")
+            if lo is None:                  # written by another mode: the masters are the bf16 weights
+                self._flat["lo"].zero_()
+            else:
+                self._flat["lo"].copy_(lo)
+            self._seen_versions = [p._version for p in self.params]
         if sd.get("exp_avg") is not None:
             if self._flat is None:
                 self._build()

@@ -1,17 +1,26 @@
-import sys, torch
-sys.path.insert(0, "/root/repo")
+"""Peak device memory of two training steps of the 2B model:  python tools/train_memory.py [BATCH] [--param-precision bf16|split_fp32|stochastic]
+("split_fp32" keeps 2 more bytes per parameter: the int16 low halves of the fp32 masters, 3.4 GB at 1.69 B parameters)."""
+import argparse, os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from orv_amd import sft, schedulers
 from orv_amd.optim import FusedAdamW
+ap = argparse.ArgumentParser()
+ap.add_argument("batch", nargs="?", type=int, default=4)
+ap.add_argument("--param-precision", default="bf16", choices=["bf16", "split_fp32", "stochastic"])
+args = ap.parse_args()
+B = args.batch
 dev = torch.device("cuda:0")
 model = bench.build_model(bench.CFG_2B, dev).train()
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 model.action_embed.forced_mask = torch.zeros(B, dtype=torch.bool)
 lat, img, prompt, actions = bench.synthetic_inputs(B, dev, torch.bfloat16)
 sched = schedulers.CogVideoXDDIMScheduler(**bench.SCHED)
-opt = FusedAdamW(model.parameters(), lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-3, max_grad_norm=1.0)
+opt = FusedAdamW(model.parameters(), lr=1e-5, betas=(0.9, 0.95), weight_decay=1e-3, max_grad_norm=1.0,
+                 param_precision=args.param_precision)
 b = sft.Batch(lat, img, prompt, actions, None, None, torch.ones(lat.shape[1], dtype=torch.bool, device=dev), 1)
 for _ in range(2):
     sft.sft_step(model, sched, opt, b)
 torch.cuda.synchronize()
-print("B=%d peak allocated %.1f GB, reserved %.1f GB" % (B, torch.cuda.max_memory_allocated() / 2**30, torch.cuda.max_memory_reserved() / 2**30))
+lo = opt._flat.get("lo")
+print("B=%d param_precision=%s peak allocated %.1f GB, reserved %.1f GB, optimizer low halves %.2f GB" % (B, args.param_precision, torch.cuda.max_memory_allocated() / 2**30, torch.cuda.max_memory_reserved() / 2**30,
+      0.0 if lo is None else lo.numel() * 2 / 2**30))
