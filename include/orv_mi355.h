@@ -287,6 +287,20 @@ int orv_adamw_flat_ex(void* p, const void* g, float* m, float* v, long n, const 
                       const unsigned char* seg_active, const int* seg_step, int nseg, float lr, float beta1, float beta2,
                       float eps, float weight_decay, int step, const float* clip_coef, void* lo, int mode, unsigned seed,
                       void* stream);
+/* orv_adamw_flat_ex with the two moments kept as block-scaled fp8 (FusedAdamW(state_precision="fp8"); the format is
+ * defined bit for bit in orv_amd/csrc/optim_s8.hip): m8 / v8 uint8[n] hold the first moment as e4m3fn and the second as e5m2 bytes in the
+ * flat layout of p, m_exp / v_exp uint8[n / 256] one scale byte e + 127 per block of 256 elements.  The update dequantises the old
+ * moments, runs the fp32 formula of orv_adamw_flat_ex with the second moment floored in the denominator at the smallest positive value
+ * of its block's incoming grid (2^(e_v_old - 16)), stores the weight by `mode` and the new moments stochastically rounded with offsets
+ * from a hash of (seed, step, flat index) only.  Inactive segments keep every byte. */
+int orv_adamw_flat_s8(void* p, const void* g, unsigned char* m8, unsigned char* v8, unsigned char* m_exp, unsigned char* v_exp, long n,
+                      const long* seg_start, const unsigned char* seg_active, const int* seg_step, int nseg, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int step, const float* clip_coef, void* lo, int mode, unsigned seed,
+                      void* stream);          /* mode 0 / 1 / 2 as orv_adamw_flat_ex; mode 0 here = nearest-even bf16 */
+/* x fp32[n] -> exactly the bytes orv_adamw_flat_s8 would store for the fp32 moments x at that (seed, step, flat index), and back
+ * (exact).  format 0 = first moment (e4m3fn), 1 = second moment (e5m2); n % 256 == 0. */
+int orv_state8_quantize(const float* x, unsigned char* q, unsigned char* exps, long n, int format, unsigned seed, int step, void* stream);
+int orv_state8_dequantize(const unsigned char* q, const unsigned char* exps, float* x, long n, int format, void* stream);
 /* dst_ptr[s][j] = bf16(src[src_off[s] + j]), j < len[s], for nseg segments (src_off / dst_ptr / len are DEVICE arrays; dst_ptr holds
  * device addresses of bf16 storage; max_len = max len[s]): the small fp32-accumulated parameter gradients go from the backward's
  * accumulator arena into the fused optimizer's flat gradient buffer in one launch (the reference leaves this to autograd's

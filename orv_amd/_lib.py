@@ -104,6 +104,10 @@ SIGNATURES = {
                                      c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
     "orv_adamw_flat_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int,
                                   c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_uint, c_void_p]),
+    "orv_adamw_flat_s8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_uint, c_void_p]),
+    "orv_state8_quantize": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_uint, c_int, c_void_p]),
+    "orv_state8_dequantize": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]),
     "orv_scatter_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "orv_sumsq": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "orv_head_transpose": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -521,6 +521,62 @@ def adamw_flat_ex(p, g, m, v, seg_start, seg_active, lr, beta1, beta2, eps, weig
                                   int(step), _p(clip_coef), _p(lo), int(mode), int(seed) & 0xFFFFFFFF, _stream()), "orv_adamw_flat_ex")
 
 
+STATE8_FORMATS = {"m": 0, "v": 1}          # first moment: e4m3fn, second moment: e5m2 (orv_amd/csrc/optim_s8.hip)
+
+
+def _need_state8(q, exps, what):
+    _need(q, torch.uint8, what), _need(exps, torch.uint8, what + "_exp")
+    if not q.is_contiguous() or not exps.is_contiguous():
+        raise RuntimeError(f"orv_amd.ops: `{what}` and `{what}_exp` must be contiguous")
+    if q.numel() % 256 or exps.numel() * 256 != q.numel():
+        raise RuntimeError(f"orv_amd.ops: `{what}` holds {q.numel()} elements, `{what}_exp` {exps.numel()} scale bytes (one per 256)")
+
+
+def adamw_flat_s8(p, g, m8, v8, m_exp, v_exp, seg_start, seg_active, lr, beta1, beta2, eps, weight_decay, step, clip_coef=None,
+                  seg_step=None, lo=None, mode=0, seed=0):
+    """``adamw_flat_ex`` on block-scaled fp8 moments: ``m8`` / ``v8`` uint8 in the layout of ``p`` (e4m3fn / e5m2 bytes), ``m_exp`` /
+    ``v_exp`` one scale byte per 256 elements.  ``mode`` as ``ADAMW_MODES`` (0 here: nearest-even bf16 of the fp32 result)."""
+    mode = ADAMW_MODES.get(mode, mode)
+    _need(p, BF16, "p"), _need(g, BF16, "g"), _need_state8(m8, m_exp, "m8"), _need_state8(v8, v_exp, "v8")
+    _need(seg_start, torch.int64, "seg_start"), _need(seg_active, torch.uint8, "seg_active")
+    if seg_step is not None:
+        _need(seg_step, torch.int32, "seg_step")
+    if clip_coef is not None:
+        _need(clip_coef, torch.float32, "clip_coef")
+    if lo is not None:
+        _need(lo, torch.int16, "lo")
+        if lo.numel() != p.numel():
+            raise RuntimeError(f"orv_amd.ops: `lo` holds {lo.numel()} elements, `p` {p.numel()}")
+    for name, t in (("p", p), ("g", g), ("seg_start", seg_start), ("seg_active", seg_active), ("seg_step", seg_step), ("lo", lo)):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+    if g.numel() < p.numel() or m8.numel() != p.numel() or v8.numel() != p.numel() or seg_start.numel() != seg_active.numel() + 1:
+        raise RuntimeError("orv_amd.ops: adamw_flat_s8 buffers do not share one flat layout")
+    check(lib().orv_adamw_flat_s8(_p(p), _p(g), _p(m8), _p(v8), _p(m_exp), _p(v_exp), p.numel(), _p(seg_start), _p(seg_active),
+                                  _p(seg_step), seg_active.numel(), float(lr), float(beta1), float(beta2), float(eps),
+                                  float(weight_decay), int(step), _p(clip_coef), _p(lo), int(mode), int(seed) & 0xFFFFFFFF, _stream()),
+          "orv_adamw_flat_s8")
+
+
+def state8_quantize(x, q, exps, fmt, seed=0, step=0):
+    """fp32 ``x`` -> the bytes ``adamw_flat_s8`` stores for these moment values at (``seed``, ``step``, flat index); ``fmt`` "m" / 0
+    (e4m3fn) or "v" / 1 (e5m2).  ``x.numel()`` must be a multiple of 256."""
+    _need(x, torch.float32, "x"), _need_state8(q, exps, "q")
+    if not x.is_contiguous() or x.numel() != q.numel():
+        raise RuntimeError(f"orv_amd.ops: `x` must be contiguous and hold the {q.numel()} elements of `q`")
+    check(lib().orv_state8_quantize(_p(x), _p(q), _p(exps), x.numel(), int(STATE8_FORMATS.get(fmt, fmt)), int(seed) & 0xFFFFFFFF,
+                                    int(step), _stream()), "orv_state8_quantize")
+
+
+def state8_dequantize(q, exps, x, fmt):
+    """The fp32 values of block-scaled fp8 moments (exact)."""
+    _need(x, torch.float32, "x"), _need_state8(q, exps, "q")
+    if not x.is_contiguous() or x.numel() != q.numel():
+        raise RuntimeError(f"orv_amd.ops: `x` must be contiguous and hold the {q.numel()} elements of `q`")
+    check(lib().orv_state8_dequantize(_p(q), _p(exps), _p(x), x.numel(), int(STATE8_FORMATS.get(fmt, fmt)), _stream()),
+          "orv_state8_dequantize")
+
+
 def sumsq(g, out):
     check(lib().orv_sumsq(_p(g), g.numel(), _p(out), _stream()), "orv_sumsq")
 

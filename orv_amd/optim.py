@@ -16,7 +16,12 @@ are fp32 (the reference keeps them in the parameter dtype).
 Parameter precision (``param_precision``): the default ``"bf16"`` rounds every updated weight back to bf16 to nearest-even, as the
 reference's bf16 training does, so an update below half a bf16 step of the weight is lost whole.  ``"split_fp32"`` keeps an exact fp32 master
 in 2 extra bytes per element (a flat int16 buffer of low halves beside the bf16 weights the model reads), ``"stochastic"`` rounds the fp32 result
-to bf16 with a 16-bit random offset drawn from a hash of (seed, step count, flat index) - unbiased, no extra memory, identical on every rank."""
+to bf16 with a 16-bit random offset drawn from a hash of (seed, step count, flat index) - unbiased, no extra memory, identical on every rank.
+
+State precision (``state_precision``): the default ``"fp32"`` keeps both moments in fp32 (8 bytes per element).  ``"fp8"`` keeps
+them as block-scaled fp8 - one byte per element (first moment e4m3fn, second e5m2) plus one scale byte per block of 256, 2 + 2/256 bytes per
+element - rounded stochastically with offsets from the same kind of hash (``seed`` is shared with the stochastic weight mode), so all ranks hold
+identical state.  It is orthogonal to ``param_precision``; the format is defined in ``orv_amd/csrc/optim_s8.hip``."""
 from __future__ import annotations
 
 from typing import Iterable, List, Optional
@@ -27,18 +32,22 @@ from . import _state, ops
 
 _SEG = 2048          # elements per workgroup of orv_adamw_flat; every segment is padded to a multiple of it
 PARAM_PRECISIONS = ("bf16", "split_fp32", "stochastic")
+STATE_PRECISIONS = ("fp32", "fp8")
+_BLOCK = 256         # elements per scale byte of the fp8 moments; divides _SEG, so a block never straddles a segment
 _AR_CHUNK = 128 * 1024 * 1024   # bf16 elements per all-reduce call (256 MB: large enough that xGMI link bandwidth, not
 #                                 launch latency, bounds the ring)
 
 
 class FusedAdamW:
     def __init__(self, params: Iterable[torch.nn.Parameter], lr=1e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-3,
-                 max_grad_norm: float = 1.0, param_precision: str = "bf16", seed: int = 0):
+                 max_grad_norm: float = 1.0, param_precision: str = "bf16", seed: int = 0, state_precision: str = "fp32"):
         if param_precision not in PARAM_PRECISIONS:
             raise ValueError(f"FusedAdamW: unknown param_precision {param_precision!r} (one of {', '.join(PARAM_PRECISIONS)})")
+        if state_precision not in STATE_PRECISIONS:
+            raise ValueError(f"FusedAdamW: unknown state_precision {state_precision!r} (one of {', '.join(STATE_PRECISIONS)})")
         if not 0 <= int(seed) < 2 ** 32:
             raise ValueError(f"FusedAdamW: seed={seed} must be a 32-bit unsigned integer")
-        self.param_precision, self.seed = param_precision, int(seed)
+        self.param_precision, self.state_precision, self.seed = param_precision, state_precision, int(seed)
         ps = [p for p in params if p.requires_grad]
         # flat-buffer order: parameters the model tagged as "gradient final when its block's backward ends" first (model order: a block's
         # six weights are contiguous), everything else behind them - see CogVideoXTransformer3DModelTraj._set_trainable_parameters and
@@ -80,11 +89,16 @@ class FusedAdamW:
             views_g.append(flat_g[off:off + p.numel()].view(p.shape))
         self._flat = dict(
             p=flat_p, g=flat_g, g_params=flat_g[:total], g_mask=flat_g[total:total + len(self.params)],
-            reduce_starts=offs + [total, total + tail], m=torch.zeros(total, dtype=torch.float32, device=dev),
-            v=torch.zeros(total, dtype=torch.float32, device=dev), views_g=views_g,
+            reduce_starts=offs + [total, total + tail], views_g=views_g, offs=offs,
             seg_start=torch.tensor(offs + [total], dtype=torch.int64, device=dev),
             active=torch.zeros(len(self.params), dtype=torch.uint8, device=dev), active_host=[False] * len(self.params),
             seg_step=torch.zeros(len(self.params), dtype=torch.int32, device=dev))
+        if self.state_precision == "fp8":
+            # all-zero bytes: every element +0 in a block of scale 2^-127, i.e. zero moments
+            z8 = lambda n: torch.zeros(n, dtype=torch.uint8, device=dev)
+            self._flat.update(m8=z8(total), v8=z8(total), m_exp=z8(total // _BLOCK), v_exp=z8(total // _BLOCK))
+        else:
+            self._flat.update(m=torch.zeros(total, dtype=torch.float32, device=dev), v=torch.zeros(total, dtype=torch.float32, device=dev))
         if self.param_precision == "split_fp32":
             # low halves of the fp32 masters, same segment layout as `p`; zeros: the master is the current bf16 value exactly
             lo = torch.zeros(total, dtype=torch.int16, device=dev)
@@ -220,7 +234,13 @@ class FusedAdamW:
             clip = clip / world
         self.step_count += 1
         f["seg_step"].add_(f["active"].to(torch.int32))          # per-parameter step counts (torch.optim.AdamW state["step"])
-        if self.param_precision == "bf16":
+        if self.state_precision == "fp8":
+            if "lo" in f:
+                self._drop_stale_param_lo()
+            ops.adamw_flat_s8(f["p"], f["g"], f["m8"], f["v8"], f["m_exp"], f["v_exp"], f["seg_start"], f["active"],
+                              self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, clip,
+                              seg_step=f["seg_step"], lo=f.get("lo"), mode=ops.ADAMW_MODES[self.param_precision], seed=self.seed)
+        elif self.param_precision == "bf16":
             ops.adamw_flat(f["p"], f["g"], f["m"], f["v"], f["seg_start"], f["active"], self.param_groups[0]["lr"], self.betas[0],
                            self.betas[1], self.eps, self.weight_decay, self.step_count, clip, seg_step=f["seg_step"])
         else:
@@ -274,15 +294,37 @@ class FusedAdamW:
         return [(p.detach().float().view(torch.int32) + lo.view(p.shape).to(torch.int32)).view(torch.float32)
                 for p, lo in zip(self.params, self._flat["views_lo"])]
 
+    # ---- moments ----
+    def _dequantized(self, q, exps, fmt):
+        x = torch.empty(q.numel(), dtype=torch.float32, device=q.device)
+        ops.state8_dequantize(q, exps, x, fmt)
+        return x
+
+    @torch.no_grad()
+    def moments(self):
+        """``(exp_avg, exp_avg_sq)``: the fp32 value of both moments of every parameter (two lists of new fp32 tensors shaped like the
+        parameters, in ``self.params`` order), in either state precision - dequantising fp8 moments is exact.  For tests and exports."""
+        if self._flat is None:
+            self._build()
+        f = self._flat
+        if self.state_precision == "fp8":
+            m, v = self._dequantized(f["m8"], f["m_exp"], "m"), self._dequantized(f["v8"], f["v_exp"], "v")
+        else:
+            m, v = f["m"], f["v"]
+        cut = lambda x: [x[o:o + p.numel()].view(p.shape).clone() for p, o in zip(self.params, f["offs"])]
+        return cut(m), cut(v)
+
     # ---- checkpointing (torch.optim-like) ----
     def state_dict(self):
         """Flat moments plus the layout they are stored in (parameter element counts and segment offsets), so that a resume
         with a different trainable set fails loudly instead of mis-assigning moments."""
         layout = [int(p.numel()) for p in self.params]
-        mode = {"param_precision": self.param_precision, "seed": self.seed}
+        mode = {"param_precision": self.param_precision, "state_precision": self.state_precision, "seed": self.seed}
+        fp8 = self.state_precision == "fp8"
+        names = {"exp_avg8": "m8", "exp_avg_sq8": "v8", "exp_avg_exp": "m_exp", "exp_avg_sq_exp": "v_exp"} if fp8 else {"exp_avg": "m", "exp_avg_sq": "v"}
         if self._flat is None:
-            return {"step": self.step_count, "exp_avg": None, "exp_avg_sq": None, "numels": layout, **mode}
-        sd = {"step": self.step_count, "exp_avg": self._flat["m"], "exp_avg_sq": self._flat["v"], "numels": layout,
+            return {"step": self.step_count, **{k: None for k in names}, "numels": layout, **mode}
+        sd = {"step": self.step_count, **{k: self._flat[b] for k, b in names.items()}, "numels": layout,
               "seg_start": self._flat["seg_start"].tolist(), "seg_step": self._flat["seg_step"], **mode}
         if "lo" in self._flat:
             self._drop_stale_param_lo()
@@ -303,7 +345,8 @@ class FusedAdamW:
         # resumed run continues it.  Checkpoints without these keys (the default mode, older builds) load into any mode.
         if sd.get("seed") is not None:
             self.seed = int(sd["seed"])
-        if self.param_precision == "split_fp32" and (sd.get("param_lo") is not None or sd.get("exp_avg") is not None):
+        have = "fp8" if sd.get("exp_avg8") is not None else "fp32" if sd.get("exp_avg") is not None else None
+        if self.param_precision == "split_fp32" and (sd.get("param_lo") is not None or have):
             if self._flat is None:
                 self._build()
             lo = sd.get("param_lo")
@@ -314,13 +357,25 @@ class FusedAdamW:
             else:
                 self._flat["lo"].copy_(lo)
             self._seen_versions = [p._version for p in self.params]
-        if sd.get("exp_avg") is not None:
+        if have:
             if self._flat is None:
                 self._build()
-            if sd["exp_avg"].numel() != self._flat["m"].numel():
+            f = self._flat
+            total = f["p"].numel()
+            keys = ("exp_avg8", "exp_avg_sq8", "exp_avg_exp", "exp_avg_sq_exp") if have == "fp8" else ("exp_avg", "exp_avg_sq")
+            want = (total, total, total // _BLOCK, total // _BLOCK)
+            if any(sd.get(k) is None or sd[k].numel() != n for k, n in zip(keys, want)):
                 raise ValueError("FusedAdamW.load_state_dict: moment buffers do not match the flat layout")
-            self._flat["m"].copy_(sd["exp_avg"])
-            self._flat["v"].copy_(sd["exp_avg_sq"])
+            dev = f["p"].device
+            if have == self.state_precision:
+                for k, b in zip(keys, ("m8", "v8", "m_exp", "v_exp") if have == "fp8" else ("m", "v")):
+                    f[b].copy_(sd[k])
+            elif have == "fp32":              # fp32 checkpoint -> fp8 state: the bytes the update kernel would have stored at (seed, step)
+                for k, q, e, fmt in (("exp_avg", "m8", "m_exp", "m"), ("exp_avg_sq", "v8", "v_exp", "v")):
+                    ops.state8_quantize(sd[k].to(dev, torch.float32).contiguous(), f[q], f[e], fmt, seed=self.seed, step=self.step_count)
+            else:                             # fp8 checkpoint -> fp32 state: exact
+                for q, e, b, fmt in (("exp_avg8", "exp_avg_exp", "m", "m"), ("exp_avg_sq8", "exp_avg_sq_exp", "v", "v")):
+                    ops.state8_dequantize(sd[q].to(dev).contiguous(), sd[e].to(dev).contiguous(), f[b], fmt)
             if sd.get("seg_step") is not None:
                 self._flat["seg_step"].copy_(sd["seg_step"])
             else:                           # checkpoints written before per-parameter counts existed
