@@ -199,6 +199,17 @@ int orv_gemm_force_epoch(void);
  * `accelerator.backward(loss)`, train_cogvideox_control_to_video_sft.py:1093; the linears of cogvideox_control.py:232-234, 263, 439-440).
  * bf16 operands, fp32 accumulation, bf16 C; accumulate != 0 adds to C (gradient accumulation).  M % 8 == 0, N % 192 == 0 or N % 256 == 0. */
 int orv_gemm_tn_bf16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, int accumulate, void* stream);
+/* C[P, Q] (+)= alpha * U[M, P]^T . V[M, Q] with min(P, Q) <= 128: the skinny sibling of orv_gemm_tn_bf16 for the weight gradients of a
+ * low-rank adapter on a linear layer, y = x W^T + b + c (x A^T) B^T: dB = c dY^T T (P = out, Q = rank) and dA = dT^T X (P = rank, Q = in),
+ * contracted over all M tokens (torch autograd of the adapter linears inside `accelerator.backward(loss)`,
+ * train_cogvideox_control_to_video_sft.py:1093).  Both operands are row-major over the contraction index M (row strides ldu / ldv elements:
+ * column slices of wider buffers are fine), bf16; accumulation is fp32.  The contraction is cut into chunks whose count and boundaries
+ * depend on (M, P, Q) only; every chunk's fp32 partial goes to `scratch` (orv_gemm_tn_skinny_scratch(M, P, Q) bytes, 16-byte aligned), the
+ * partials are added in chunk order, scaled by alpha, the old C is added in fp32 when accumulate != 0, and the sum is rounded to bf16 once.
+ * No atomics: two runs give identical bits.  P % 16 == 0, Q % 16 == 0, M >= 1, ldu / ldv / ldc multiples of 8, 16-byte aligned pointers. */
+long orv_gemm_tn_skinny_scratch(int M, int P, int Q);
+int orv_gemm_tn_skinny_bf16(const void* U, long ldu, const void* V, long ldv, void* C, long ldc, int M, int P, int Q, float alpha,
+                            int accumulate, void* scratch, void* stream);
 
 /* -- MXFP8 inference GEMMs (opt-in: CogVideoXTransformer3DModelTraj.enable_mxfp8) ------------------------------------------------- */
 /* Format (OCP MX, e4m3fn elements): a row-major [rows, K] bf16 matrix (K % 32 == 0) is cut into blocks of 32 consecutive K elements;

@@ -65,6 +65,9 @@ SIGNATURES = {
     "orv_gemm_force_tile": (c_int, [c_int, c_int, c_int]),
     "orv_gemm_force_epoch": (c_int, []),
     "orv_gemm_tn_bf16": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p]),
+    "orv_gemm_tn_skinny_scratch": (c_long, [c_int, c_int, c_int]),
+    "orv_gemm_tn_skinny_bf16": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_float, c_int, c_void_p,
+                                        c_void_p]),
     "orv_gemm_bf16": (c_int, [POINTER(Gemm), c_void_p]),
     "orv_packed_rows": (c_long, [c_long]),
     "orv_mxfp8_quantize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_void_p]),

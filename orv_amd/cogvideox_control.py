@@ -32,7 +32,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 import torch
 from torch import nn
 
-from . import _state, ops
+from . import _state, lora as _lora, ops
 from .components import ActionEmbed, ActionRecon, Transformer3DModelTrajOutput
 from .embeddings import sincos_3d
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler, retrieve_timesteps
@@ -316,7 +316,7 @@ _CONFIG_DEFAULTS = dict(
     recon_action=False, visual_guidance=False, num_control_keys=2, multiview=False, max_n_view=3, from_t2v=False)
 
 
-class CogVideoXTransformer3DModelTraj(nn.Module):
+class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
     """Trajectory/occupancy-conditioned CogVideoX 3-D DiT (:448-1087)."""
 
     config_name = "config.json"
@@ -394,6 +394,7 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
         self._mxfp8 = False         # MXFP8 inference mode of the block GEMMs (enable_mxfp8)
         self._mx_gen = 0            # bumped by every enable_mxfp8 call: part of GraphedTransformer's key
         self._mx_cache = None       # per block: (weight key, quantised QKV / out / FFN1 / FFN2 weights)
+        self._lora_init()           # LoRA adapters of the attention projections (orv_amd/lora.py)
         self._set_zeros()
         self._set_trainable_parameters()
 
@@ -441,6 +442,9 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
         here (on the first forward when the model is not yet a bf16 model on the GPU) and again whenever a block weight changes (in-place
         edits, moves, replaced Parameters).  Inference only: a forward in training mode or with gradients raises RuntimeError.
         ``enable_mxfp8(False)`` returns to the bf16 path bit for bit and frees the quantised weights.  Returns ``self``."""
+        if enabled and self._lora_runtime() is not None:
+            raise RuntimeError("MXFP8 mode runs fused adapters only: fuse_lora() (the fused weights are quantised), disable_adapters() or "
+                               "delete_adapter() before enable_mxfp8()")
         self._mxfp8 = bool(enabled)
         self._mx_gen += 1
         self._mx_cache = None
@@ -752,6 +756,10 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
                                "requires_grad_(False)), or turn it off with enable_mxfp8(False) before training")
         if not hidden_states.is_cuda:
             raise RuntimeError("orv_amd runs on MI355X only: move the model and its inputs to the GPU (no CPU fallback)")
+        # attention_kwargs["scale"] multiplies the active adapter's coefficient for this call (:729-741); ignored without an adapter
+        lora_rt = self._lora_runtime((attention_kwargs or {}).get("scale", 1.0)) if self._lora_active is not None else None
+        if lora_rt is not None and self._mxfp8:
+            raise RuntimeError("MXFP8 mode runs fused adapters only: fuse_lora(), disable_adapters() or enable_mxfp8(False)")
         if self.dtype != BF16:
             raise RuntimeError(f"orv_amd kernels are bf16: call model.to(torch.bfloat16) (got {self.dtype}).  The reference's "
                                "`--dtype float16` (inference_control_to_video.py:198-203) is not provided - its default and every shipped "
@@ -761,15 +769,17 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             # training step (train_cogvideox_control_to_video_sft.py:1051-1093): forward that saves activations, with the
             # hand-written backward attached to autograd as one node
+            if self._lora_fused is not None:
+                raise RuntimeError("an adapter is fused into the weights: unfuse_lora() before a forward that records gradients")
             from .training import forward_with_grad
             out, mask, recon = forward_with_grad(self, hidden_states, encoder_hidden_states, controls_or_guidances, timestep,
-                                                 ofs, image_rotary_emb, num_views, image_rotary_emb_view)
+                                                 ofs, image_rotary_emb, num_views, image_rotary_emb_view, lora=lora_rt)
             if not return_dict:
                 return (out, mask, recon)
             return Transformer3DModelTrajOutput(sample=out, is_action_mask=mask, actions_recon=recon)
         with torch.no_grad():
             return self._forward_inference(hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs,
-                                           image_rotary_emb, return_dict, num_views, image_rotary_emb_view)
+                                           image_rotary_emb, return_dict, num_views, image_rotary_emb_view, lora=lora_rt)
 
     # ---- multiview (:273-348, :797-800) ----
     def _mv_state(self, b, v, f, Nt, P, S, dev):
@@ -836,8 +846,52 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
         # '(b f) (v s) d -> (b v) (f s) d' + gated residual on the video rows only (the text output of attn1 is dropped)
         ops.scatter_gated_rows(mv["att"], mv["idx"], m[:, 1, 2 * D:], 2 * 3 * D, x, R, D, S, Nt)
 
+    def _base_attention(self, blk, ws, packed, m1, mb, mg, grp, B, S, Nt, rope, scale):
+        """norm1 -> q | k | v -> attention -> gated out-projection residual of one block (:394-437), packed operands where the plan says so."""
+        c = self.config
+        D, heads = self.inner_dim, c.num_attention_heads
+        M = B * S
+        x, xn, qkv, att, s_pad = ws["x"], ws["xn"], ws["qkv"], ws["att"], ws["s_pad"]
+        at = blk.attn1
+        ops.layernorm_modulate(x, xn, blk.norm1.norm.weight, blk.norm1.norm.bias, m1[..., D:2 * D], m1[..., :D],
+                               mb, mg, grp, B, D, c.norm_eps, out_packed=packed["qkv"])
+        self._qkv_projection(at, xn, qkv, rope, B, S, heads, Nt, s_pad, scale, a_packed=packed["qkv"])
+        bound = at.score_bound(scale, rope is not None)
+        # packed path: the attention kernel writes its output, the FFN1 GELU epilogue the hidden state, in the P16 layout the d8 GEMM reads
+        att_p = packed["out"] and ws["attn_ws"] is None and ops.attention_packed_ok(bound, 1.0 / LOG2E)
+        if att_p:
+            ops.attention_fwd(qkv, None, att, B, S, heads, s_pad, 1.0 / LOG2E, score_bound=bound, out_packed=True)
+        else:
+            ops.attention_fwd(qkv, None, att, B, S, heads, s_pad, 1.0 / LOG2E, score_bound=bound, ws=ws["attn_ws"])
+        ops.gemm(att, at.to_out[0].weight, at.to_out[0].bias, x, M, D, D, epilogue=2, R=x, ldr=D,
+                 gate=m1[..., 2 * D:], gate_b=mb, gate_g=mg, grp=grp, a_packed=att_p)
+
+    def _lora_attention(self, blk, lbw, lora, ws, m1, mb, mg, grp, B, S, Nt, rope, scale):
+        """The same with an active LoRA adapter (orv_amd/lora.py): row-major operands throughout; the rank updates are added to the raw
+        q | k | v projection before ``orv_qkv_prep`` and to the residual stream before the unchanged out-projection launch."""
+        c = self.config
+        D, heads = self.inner_dim, c.num_attention_heads
+        M = B * S
+        x, xn, qkv, att, s_pad = ws["x"], ws["xn"], ws["qkv"], ws["att"], ws["s_pad"]
+        at = blk.attn1
+        need = M * 3 * lora.rp
+        if ws.get("lora_t") is None or ws["lora_t"].numel() < need:
+            ws["lora_t"] = torch.empty(need, dtype=BF16, device=x.device)
+        T = ws["lora_t"]
+        ops.layernorm_modulate(x, xn, blk.norm1.norm.weight, blk.norm1.norm.bias, m1[..., D:2 * D], m1[..., :D], mb, mg, grp, B, D, c.norm_eps)
+        if lbw.nT:
+            _lora.qkv_projection(at, lbw, lora, xn, qkv, T[:M * lbw.nT * lora.rp].view(M, lbw.nT * lora.rp), rope, B, S, heads, Nt, s_pad, scale)
+        else:
+            self._qkv_projection(at, xn, qkv, rope, B, S, heads, Nt, s_pad, scale)
+        bound = at.score_bound(scale, rope is not None)
+        ops.attention_fwd(qkv, None, att, B, S, heads, s_pad, 1.0 / LOG2E, score_bound=bound, ws=ws["attn_ws"])
+        if lbw.out_params is not None:
+            _lora.out_update(lbw, lora, att, T[:M * lora.rp].view(M, lora.rp), x, x, M, D, m1[..., 2 * D:], mb, mg, grp)
+        ops.gemm(att, at.to_out[0].weight, at.to_out[0].bias, x, M, D, D, epilogue=2, R=x, ldr=D, gate=m1[..., 2 * D:], gate_b=mb, gate_g=mg,
+                 grp=grp)
+
     def _forward_inference(self, hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs,
-                           image_rotary_emb, return_dict, num_views=1, image_rotary_emb_view=None):
+                           image_rotary_emb, return_dict, num_views=1, image_rotary_emb_view=None, lora=None):
         c = self.config
         dev = hidden_states.device
         if num_views > 1:                                                            # :756-758
@@ -979,18 +1033,11 @@ class CogVideoXTransformer3DModelTraj(nn.Module):
                 self._mx_block(blk, mxw[i], ws, m1, m2, mb, mg, grp, B, S, Nt, rope, scale)
                 continue
             at = blk.attn1
-            ops.layernorm_modulate(x, xn, blk.norm1.norm.weight, blk.norm1.norm.bias, m1[..., D:2 * D], m1[..., :D],
-                                   mb, mg, grp, B, D, c.norm_eps, out_packed=packed["qkv"])
-            self._qkv_projection(at, xn, qkv, rope, B, S, heads, Nt, s_pad, scale, a_packed=packed["qkv"])
-            bound = at.score_bound(scale, rope is not None)
-            # packed path: the attention kernel writes its output, the FFN1 GELU epilogue the hidden state, in the P16 layout the d8 GEMM reads
-            att_p = packed["out"] and ws["attn_ws"] is None and ops.attention_packed_ok(bound, 1.0 / LOG2E)
-            if att_p:
-                ops.attention_fwd(qkv, None, att, B, S, heads, s_pad, 1.0 / LOG2E, score_bound=bound, out_packed=True)
+            lbw = lora.block(i) if lora is not None else None
+            if lbw is not None:
+                self._lora_attention(blk, lbw, lora, ws, m1, mb, mg, grp, B, S, Nt, rope, scale)
             else:
-                ops.attention_fwd(qkv, None, att, B, S, heads, s_pad, 1.0 / LOG2E, score_bound=bound, ws=ws["attn_ws"])
-            ops.gemm(att, at.to_out[0].weight, at.to_out[0].bias, x, M, D, D, epilogue=2, R=x, ldr=D,
-                     gate=m1[..., 2 * D:], gate_b=mb, gate_g=mg, grp=grp, a_packed=att_p)
+                self._base_attention(blk, ws, packed, m1, mb, mg, grp, B, S, Nt, rope, scale)
             ops.layernorm_modulate(x, xn, blk.norm2.norm.weight, blk.norm2.norm.bias, m2[..., D:2 * D], m2[..., :D],
                                    mb, mg, grp, B, D, c.norm_eps, out_packed=packed["ffn1"])
             f0, f2 = blk.ff.net[0].proj, blk.ff.net[2]
@@ -1232,10 +1279,18 @@ class GraphedTransformer:
 
     def __call__(self, hidden_states, encoder_hidden_states, timestep, **kw):
         kw = dict(kw, hidden_states=hidden_states, encoder_hidden_states=encoder_hidden_states, timestep=timestep)
+        akw = kw.pop("attention_kwargs", None)
         leaves, desc = self._flatten(kw)
+        # adapter state: generation (add / set / delete / enable / fuse), active name and this call's scale; in-place edits of adapter
+        # values move the parameters' _version sum / the weights epoch like any other weight
+        lkey = self.tr._lora_key((akw or {}).get("scale", 1.0)) if getattr(self.tr, "_lora_active", None) is not None else None
+        if akw is not None:
+            if any(torch.is_tensor(v) for v in akw.values()):
+                raise _NotCapturable("GraphedTransformer: tensor entries in attention_kwargs")
+            kw["attention_kwargs"] = akw
         # MXFP8 state: a graph captured in one mode never replays in the other, nor after a re-enable (new quantised weights)
         mx = (self.tr._mx_gen,) if getattr(self.tr, "_mxfp8", False) else None
-        key = (desc, _state.weights_epoch[0], self._weights_version(), self.tr.training, _chains(), mx)
+        key = (desc, _state.weights_epoch[0], self._weights_version(), self.tr.training, _chains(), mx, lkey)
         st = self._state.get(key)
         if st is None:                       # eager warm-up call
             st = self._state[key] = {"calls": 1}
@@ -1271,6 +1326,7 @@ class GraphedTransformer:
                 with torch.no_grad():
                     return self._forward(kw, st, concurrent=False)
             st["graph"] = g                                              # kept alive even if the model later swaps in another one
+            st["lora"] = getattr(self.tr, "_lora_cached_operands", lambda: None)()   # the adapter operand copies the captured launches read
         else:
             for dst, src in zip(st["static"], leaves):
                 if dst.data_ptr() != src.data_ptr():
@@ -1502,6 +1558,45 @@ class CogVideoXImageToVideoPipelineTraj:
         z = latents.permute(0, 2, 1, 3, 4) / self.vae_scaling_factor_image
         out = self.vae.decode(z)
         return getattr(out, "sample", out)
+
+    # ---- LoRA (diffusers ``CogVideoXLoraLoaderMixin`` subset; the adapters live on the transformer, orv_amd/lora.py) ----
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None, **kwargs):
+        """Loads ``pytorch_lora_weights.safetensors`` (directory, file or state dict with ``transformer.``-prefixed keys) into the
+        transformer and makes it the active adapter."""
+        self.transformer.load_lora_adapter(pretrained_model_name_or_path_or_dict, adapter_name=adapter_name or "default",
+                                           prefix="transformer")
+        self.transformer.set_adapter(adapter_name or "default")
+
+    def unload_lora_weights(self):
+        tr = self.transformer
+        tr.unfuse_lora()
+        for name in list(tr._lora_adapters):
+            tr.delete_adapter(name)
+
+    def fuse_lora(self, lora_scale: float = 1.0, **kwargs):
+        self.transformer.fuse_lora(lora_scale=lora_scale)
+
+    def unfuse_lora(self, **kwargs):
+        self.transformer.unfuse_lora()
+
+    @classmethod
+    def save_lora_weights(cls, save_directory, transformer_lora_layers: Dict[str, torch.Tensor] = None, is_main_process: bool = True,
+                          transformer_lora_adapter_metadata: Optional[Dict[str, Any]] = None, **kwargs):
+        """Writes ``transformer_lora_layers`` (``transformer.get_adapter_state_dict()``: keys without a prefix) as
+        ``pytorch_lora_weights.safetensors`` with ``transformer.``-prefixed keys; ``transformer_lora_adapter_metadata`` (``r``,
+        ``lora_alpha``, ``use_rslora``) goes into the file's ``lora_adapter_metadata`` entry."""
+        from safetensors.torch import save_file
+        if not transformer_lora_layers:
+            raise ValueError("You must pass `transformer_lora_layers`.")
+        if not is_main_process:
+            return
+        os.makedirs(save_directory, exist_ok=True)
+        sd = {(k if k.startswith("transformer.") else "transformer." + k): v.detach().to("cpu").contiguous()
+              for k, v in transformer_lora_layers.items()}
+        meta = {"format": "pt"}
+        if transformer_lora_adapter_metadata:
+            meta["lora_adapter_metadata"] = json.dumps(dict(transformer_lora_adapter_metadata), sort_keys=True)
+        save_file(sd, os.path.join(save_directory, _lora.LORA_WEIGHT_NAME), metadata=meta)
 
     def enable_hip_graph(self, enabled: bool = True):
         """Force (``True``) or forbid (``False``) replaying the transformer forward of each denoise step from a HIP graph (see

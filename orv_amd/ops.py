@@ -200,6 +200,25 @@ def gemm_tn(A, W, C, M, N, K, accumulate=False, lda=None, ldw=None, ldc=None):
     return C
 
 
+def gemm_tn_skinny_scratch(M, P, Q) -> int:
+    """Bytes of fp32 scratch ``gemm_tn_skinny`` needs for this shape."""
+    return int(lib().orv_gemm_tn_skinny_scratch(int(M), int(P), int(Q)))
+
+
+def gemm_tn_skinny(U, V, C, M, P, Q, alpha=1.0, accumulate=False, ldu=None, ldv=None, ldc=None, scratch=None):
+    """C[P, Q] (+)= alpha * U[M, P]^T . V[M, Q], min(P, Q) <= 128 (adapter weight gradients; deterministic, split over the M rows).
+    ``scratch``: a uint8 / fp32 CUDA tensor of at least ``gemm_tn_skinny_scratch(M, P, Q)`` bytes (allocated when omitted)."""
+    _need(U, BF16, "U"), _need(V, BF16, "V"), _need(C, BF16, "C")
+    need = gemm_tn_skinny_scratch(M, P, Q)
+    if scratch is None:
+        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=U.device)
+    elif not scratch.is_cuda or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"gemm_tn_skinny: scratch must be a CUDA tensor of at least {need} bytes")
+    check(lib().orv_gemm_tn_skinny_bf16(_p(U), ldu or P, _p(V), ldv or Q, _p(C), ldc or Q, M, P, Q, float(alpha), int(bool(accumulate)),
+                                        _p(scratch), _stream()), "orv_gemm_tn_skinny_bf16")
+    return C
+
+
 def modulation_tables(temb, action_emb, w_ptrs, b_ptrs, n_tab, B, T, E, width, text, out=None):
     """All AdaLN tables of a forward: out fp32 [n_tab, B, 1+T, width]; w_ptrs/b_ptrs int64 device tensors of pointers."""
     _need(temb, BF16, "temb")

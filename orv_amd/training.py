@@ -20,7 +20,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _state, ops
+from . import _state, lora as _lora, ops
 
 _SCATTER_GRADS = os.environ.get("ORV_SCATTER_GRADS", "1") != "0"      # A/B switch (small gradients: arena -> flat buffer directly)
 
@@ -132,22 +132,28 @@ class _AttnBufs:
         self.nd = torch.empty(B_, heads, self.s_pad, dtype=torch.float32, device=dev)
 
 
-def _attn_forward(at, xn, ly, bufs, B_, S_, n_text, heads, rope, scale):
-    """QKV GEMM -> qk LayerNorm / RoPE / V^T -> flash attention; keeps qkv_raw, att, lse on ``ly``."""
+def _attn_forward(at, xn, ly, bufs, B_, S_, n_text, heads, rope, scale, lbw=None, lora=None):
+    """QKV GEMM -> qk LayerNorm / RoPE / V^T -> flash attention; keeps qkv_raw, att, lse on ``ly``.  ``lbw`` / ``lora``: the block's LoRA
+    operands (orv_amd/lora.py) - the rank updates join the raw projection, T = xn Acat^T is kept on ``ly`` for the adapter gradients."""
     D = heads * 64
     M_ = B_ * S_
     dev = xn.device
     from .cogvideox_control import CogVideoXTransformer3DModelTraj as _M
     ly.qkv_raw = torch.empty(M_, 3 * D, dtype=BF16, device=dev)       # raw projection: input of the qk-LayerNorm adjoint
     ly.qkvn = torch.empty(M_, 3 * D, dtype=BF16, device=dev)          # q' | k' | v as the attention kernels read them (kept:
-    _M._qkv_projection(at, xn, ly.qkvn, rope, B_, S_, heads, n_text, bufs.s_pad, scale, raw=ly.qkv_raw)   # 148 MB/layer)
+    if lbw is not None and lbw.nT:
+        ly.lora_t = torch.empty(M_, lbw.nT * lora.rp, dtype=BF16, device=dev)
+        _lora.qkv_projection(at, lbw, lora, xn, ly.qkvn, ly.lora_t, rope, B_, S_, heads, n_text, bufs.s_pad, scale, raw=ly.qkv_raw)
+    else:
+        _M._qkv_projection(at, xn, ly.qkvn, rope, B_, S_, heads, n_text, bufs.s_pad, scale, raw=ly.qkv_raw)   # 148 MB/layer)
     ly.att = torch.empty(M_, D, dtype=BF16, device=dev)
     ly.lse = torch.empty(B_, heads, S_, dtype=torch.float32, device=dev)
     ops.attention_fwd(ly.qkvn, None, ly.att, B_, S_, heads, bufs.s_pad, 1.0 / LOG2E, lse=ly.lse, score_bound_dev=at.score_bound_dev(scale))
 
 
-def _attn_backward(at, ly, xn, datt, bufs, B_, S_, n_text, heads, rope, scale, grads, f32_to_param_grad, z32):
-    """Adjoint of ``_attn_forward``: datt [M, D] -> gradient w.r.t. xn [M, D]; parameter gradients into ``grads``."""
+def _attn_backward(at, ly, xn, datt, bufs, B_, S_, n_text, heads, rope, scale, grads, f32_to_param_grad, z32, lbw=None, lora=None):
+    """Adjoint of ``_attn_forward``: datt [M, D] -> gradient w.r.t. xn [M, D]; parameter gradients into ``grads``.  With LoRA operands
+    the q / k / v adapters' adjoints follow the base dgrad: dT_j = dqkv_j (c B_j), dB_j, dA_j (skinny kernel), dxn += dT Acat."""
     D = heads * 64
     M_ = B_ * S_
     dev = xn.device
@@ -190,6 +196,13 @@ def _attn_backward(at, ly, xn, datt, bufs, B_, S_, n_text, heads, rope, scale, g
             f32_to_param_grad(lin.bias, bs[j * D:(j + 1) * D])
     dxn = torch.empty(M_, D, dtype=BF16, device=dev)
     _dgrad(dqkv, wqkv, dxn, M_, 3 * D, D)
+    if lbw is not None and lbw.nT:
+        rp, W = lora.rp, lbw.nT * lora.rp
+        dT = torch.empty(M_, W, dtype=BF16, device=dev)
+        for slot, j in enumerate(lbw.qkv):
+            _lora.linear_backward(lora, lbw.qkv_params[slot], dqkv[:, j * D:], 3 * D, ly.lora_t[:, slot * rp:], W, xn, D, lbw.cBT[slot],
+                                  dT[:, slot * rp:], W, M_, D, D, grads)
+        ops.gemm(dT, lbw.AcatT, None, dxn, M_, D, W, epilogue=2, R=dxn, ldr=D)
     return dxn
 
 
@@ -205,7 +218,7 @@ def _mv_index(b, v, f, Nt, P, S, dev):
 
 
 def forward_train(model, hidden_states, encoder_hidden_states, controls, timestep, ofs=None, image_rotary_emb=None,
-                  num_views=1, image_rotary_emb_view=None):
+                  num_views=1, image_rotary_emb_view=None, lora=None):
     """Same arithmetic as ``CogVideoXTransformer3DModelTraj.forward`` (inference kernels), keeping what backward needs."""
     c = model.config
     dev = hidden_states.device
@@ -408,10 +421,20 @@ def forward_train(model, hidden_states, encoder_hidden_states, controls, timeste
         ly.xn1 = e(M, D)
         ops.layernorm_modulate(x, ly.xn1, blk.norm1.norm.weight, blk.norm1.norm.bias, m1[..., D:2 * D], m1[..., :D], mb, mg,
                                grp, B, D, c.norm_eps)
-        _attn_forward(at, ly.xn1, ly, bufs, B, S, Nt, heads, rope, scale)
+        lbw = lora.block(i, train=True) if lora is not None else None
+        _attn_forward(at, ly.xn1, ly, bufs, B, S, Nt, heads, rope, scale, lbw, lora)
         ly.x1, ly.y1 = e(M, D), e(M, D)
-        ops.gemm(ly.att, at.to_out[0].weight, at.to_out[0].bias, ly.x1, M, D, D, epilogue=2, R=x, ldr=D, gate=m1[..., 2 * D:],
+        res = x
+        if lbw is not None and lbw.out_params is not None:
+            # x1 = x + gate c (att A^T) B^T first, then the unchanged base launch on top; y1 (the gate's adjoint needs the whole branch output)
+            # is the sum of both launches' pre-gate outputs
+            ly.lora_to, y1l = e(M, lora.rp), e(M, D)
+            _lora.out_update(lbw, lora, ly.att, ly.lora_to, x, ly.x1, M, D, m1[..., 2 * D:], mb, mg, grp, Y=y1l)
+            res = ly.x1
+        ops.gemm(ly.att, at.to_out[0].weight, at.to_out[0].bias, ly.x1, M, D, D, epilogue=2, R=res, ldr=D, gate=m1[..., 2 * D:],
                  gate_b=mb, gate_g=mg, grp=grp, Y=ly.y1, ldy=D)
+        if res is not x:
+            ops.add_rows(ly.y1, None, y1l, ly.y1, 0, M, D)
         ly.xn2 = e(M, D)
         ops.layernorm_modulate(ly.x1, ly.xn2, blk.norm2.norm.weight, blk.norm2.norm.bias, m2[..., D:2 * D], m2[..., :D], mb,
                                mg, grp, B, D, c.norm_eps)
@@ -453,6 +476,7 @@ def forward_train(model, hidden_states, encoder_hidden_states, controls, timeste
     #  activations are released by reference counting the moment the autograd node dies - a cycle here kept the previous step's
     #  ~100 GB alive until the next garbage collection: 5B went from 329 to 889 ms per step and 105 to 200 GiB)
     sv.recompute = recompute
+    sv.lora = lora
     sv.x_last = x
     gv = ops.groups(Nv, 0, per_group)
     sv.vis, sv.vis2 = e(B * Nv, D), e(B * Nv, D)
@@ -621,7 +645,12 @@ def backward(model, sv, dout, drecon=None, grad_hook=None) -> Dict[int, torch.Te
         wgrad_p(wo.weight, dy1, ly.att, M, D, D, bias=wo.bias)
         datt = e(M, D)
         _dgrad(dy1, wo.weight, datt, M, D, D)
-        dxn1 = _attn_backward(at, ly, ly.xn1, datt, bufs, B, S, Nt, heads, sv.rope, scale, grads, f32_to_param_grad, z32)
+        lbw = sv.lora.block(i, train=True) if sv.lora is not None else None
+        if lbw is not None and lbw.out_params is not None:
+            dTo = e(M, sv.lora.rp)
+            _lora.linear_backward(sv.lora, lbw.out_params, dy1, D, ly.lora_to, sv.lora.rp, ly.att, D, lbw.ocBT, dTo, sv.lora.rp, M, D, D, grads)
+            ops.gemm(dTo, lbw.oAT, None, datt, M, D, sv.lora.rp, epilogue=2, R=datt, ldr=D)
+        dxn1 = _attn_backward(at, ly, ly.xn1, datt, bufs, B, S, Nt, heads, sv.rope, scale, grads, f32_to_param_grad, z32, lbw, sv.lora)
         dx0 = e(M, D)
         dg, db_ = z32(D), z32(D)
         ops.layernorm_modulate_bwd(dxn1, ly.x0, dx1, dx0, blk.norm1.norm.weight, blk.norm1.norm.bias, m1[..., D:2 * D],
@@ -838,10 +867,10 @@ class DiTFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, hidden_states, encoder_hidden_states, controls, timestep, ofs, image_rotary_emb, num_views,
-                image_rotary_emb_view, *params):
+                image_rotary_emb_view, lora, *params):
         with torch.no_grad():
             out, is_mask, recon, sv = forward_train(model, hidden_states, encoder_hidden_states, controls, timestep, ofs,
-                                                    image_rotary_emb, num_views, image_rotary_emb_view)
+                                                    image_rotary_emb, num_views, image_rotary_emb_view, lora=lora)
         ctx.model, ctx.sv, ctx.params = model, sv, params
         dev = out.device
         if is_mask is None:
@@ -862,12 +891,12 @@ class DiTFunction(torch.autograd.Function):
         for p_ in ctx.params:
             g = grads.get(id(p_))
             outs.append(g.to(p_.dtype) if (g is not None and p_.requires_grad) else None)
-        return (None, None, None, None, None, None, None, None, None, *outs)
+        return (None, None, None, None, None, None, None, None, None, None, *outs)
 
 
 def forward_with_grad(model, hidden_states, encoder_hidden_states, controls, timestep, ofs=None, image_rotary_emb=None,
-                      num_views=1, image_rotary_emb_view=None):
+                      num_views=1, image_rotary_emb_view=None, lora=None):
     params = tuple(p_ for p_ in model.parameters())
     out, is_mask, recon = DiTFunction.apply(model, hidden_states, encoder_hidden_states, controls, timestep, ofs,
-                                            image_rotary_emb, num_views, image_rotary_emb_view, *params)
+                                            image_rotary_emb, num_views, image_rotary_emb_view, lora, *params)
     return out, (is_mask if is_mask.numel() else None), (recon if recon.numel() else None)
