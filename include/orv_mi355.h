@@ -371,6 +371,32 @@ float orv_attention_static_limit(int aligned_out);
 int orv_attention_fwd_bounded_dev(const void* qkv, int ld_qkv, void* out, int ld_out, float* lse, int B, int S, int H, float scale,
                                   const float* score_bound_dev, void* stream);
 
+/* -- T5 text encoder (orv_amd.t5.T5EncoderModel) ------------------------------------------------------------------------------------ */
+/* The reference encodes prompts with transformers' T5EncoderModel, `text_encoder(ids)[0]` (orv/models/text_encoder.py:34, called from
+ * the pipeline at orv/models/cogvideox_control.py:1290-1299).  These three kernels are what that encoder (T5 v1.1: RMS LayerNorm, unscaled
+ * attention with a relative-position bias, gated-GELU FFN, no biases) needs beside orv_gather_rows (the embedding) and orv_gemm_bf16 (the
+ * projections; the residual adds are its epilogue 2 with R == C).  All three validate before any launch, never allocate, use no atomics
+ * (two runs are bit-identical) and are stream-ordered. */
+/* out[b, i, h, :] = sum_j softmax_j(q_i . k_j + bias_rel[h, j - i + S - 1]) v_j: T5 self-attention (transformers T5Attention.forward as
+ * reached from orv/models/text_encoder.py:34 and cogvideox_control.py:1290-1299): NO 1/sqrt(d) scale, the bias added in fp32 before the
+ * row maximum, the true row maximum subtracted (scores are unbounded), no key mask (the reference passes no attention_mask).  qkv
+ * [B S, ld_qkv] bf16 packed as orv_attention_fwd reads it (q at column h*64, k at H*64 + h*64, v at 2*H*64 + h*64; head_dim 64); bias_rel
+ * fp32 [H, 2S - 1], entry j - i + S - 1 = the bias of query i and key j; out [B S, ld_out] bf16, columns [0, H*64) of rows [0, B S)
+ * written and nothing else.  fp32 accumulation on the MFMA.  1 <= S <= orv_t5_attention_max_seq() (512: one head's K and V stay in one
+ * workgroup's LDS); a longer S is an error that names the maximum.  ld_qkv, ld_out multiples of 8, 16-byte aligned pointers. */
+int orv_t5_attention_max_seq(void);
+int orv_t5_attention_fwd(const void* qkv, int ld_qkv, const float* bias_rel, void* out, int ld_out, int B, int S, int H, void* stream);
+/* y[m, :] = w * bf16(x[m, :] * rsqrt(mean(x[m, :]^2) + eps)): transformers T5LayerNorm.forward (no mean subtraction, no bias; statistics
+ * in fp32, the normalised row rounded to bf16 before the gain as there) - every layer_norm / final_layer_norm of the encoder behind
+ * orv/models/text_encoder.py:34 and cogvideox_control.py:1290-1299.  x, y [M, D] bf16 (row strides ldx / ldy, multiples of 8), w [D]
+ * bf16; D % 64 == 0; x == y is allowed. */
+int orv_t5_rmsnorm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int D, float eps, void* stream);
+/* out[m, f] = gelu_tanh(h[m, f]) * h[m, F + f], fp32, rounded to bf16 once: the gate of transformers T5DenseGatedActDense
+ * ("gated-gelu": gelu_new(wi_0 x) * wi_1 x) inside the encoder of orv/models/text_encoder.py:34 / cogvideox_control.py:1290-1299, with
+ * both wi projections coming from ONE orv_gemm_bf16 over the stacked weight [2 d_ff, d_model].  h [M, 2F] bf16 (row stride ldh), out
+ * [M, F] bf16 (row stride ldo); F % 8 == 0, strides multiples of 8. */
+int orv_geglu(const void* h, int ldh, void* out, int ldo, int M, int F, void* stream);
+
 /* -- sampler ---------------------------------------------------------------------------------- */
 /* One fused scheduler update on n elements (cogvideox_control.py:1433-1459 + diffusers
  * CogVideoXDDIMScheduler.step / CogVideoXDPMScheduler.step, v-prediction):

@@ -127,6 +127,10 @@ SIGNATURES = {
     "orv_vae_groupnorm_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
     "orv_vae_norm_apply": (c_int, [c_void_p] * 7 + [c_int] * 9 + [c_float, c_int, c_int, c_void_p]),
     "orv_vae_blend": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "orv_t5_attention_max_seq": (c_int, []),
+    "orv_t5_attention_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "orv_t5_rmsnorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "orv_geglu": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -24,24 +24,30 @@ def _parse_size(s: Union[int, str]) -> int:
     return int(s)
 
 
-def load_state_dict_dir(directory: str) -> Dict[str, torch.Tensor]:
+def load_state_dict_dir(directory: str, weights_name: str = WEIGHTS_NAME, index_name: str = INDEX_NAME,
+                        pattern: str = "diffusion_pytorch_model*.safetensors") -> Dict[str, torch.Tensor]:
+    """``weights_name`` / ``index_name`` / ``pattern``: the file names of another library's layout (transformers writes
+    ``model.safetensors`` / ``model.safetensors.index.json``: orv_amd.t5); the defaults are the diffusers names above."""
     from safetensors.torch import load_file
-    index = os.path.join(directory, INDEX_NAME)
+    index = os.path.join(directory, index_name)
     if os.path.exists(index):
         with open(index, "r", encoding="utf-8") as f:
             files = sorted(set(json.load(f)["weight_map"].values()))
     else:
-        files = [os.path.basename(p) for p in sorted(glob.glob(os.path.join(directory, "diffusion_pytorch_model*.safetensors")))]
+        files = [os.path.basename(p) for p in sorted(glob.glob(os.path.join(directory, pattern)))]
     if not files:
-        raise RuntimeError(f"no diffusion_pytorch_model*.safetensors under {directory}")
+        raise RuntimeError(f"no {pattern} under {directory}")
     state: Dict[str, torch.Tensor] = {}
     for fn in files:
         state.update(load_file(os.path.join(directory, fn)))
     return state
 
 
-def save_state_dict_dir(state: Dict[str, torch.Tensor], directory: str, max_shard_size: Union[int, str] = "5GB") -> None:
+def save_state_dict_dir(state: Dict[str, torch.Tensor], directory: str, max_shard_size: Union[int, str] = "5GB",
+                        weights_name: str = WEIGHTS_NAME, index_name: str = INDEX_NAME) -> None:
+    """Shards are named after ``weights_name`` (``<stem>-00001-of-0000N.safetensors``) and indexed by ``index_name``."""
     from safetensors.torch import save_file
+    stem = weights_name[: -len(".safetensors")]
     limit = _parse_size(max_shard_size)
     shards, cur, cur_bytes = [], {}, 0
     for k, v in state.items():
@@ -53,14 +59,14 @@ def save_state_dict_dir(state: Dict[str, torch.Tensor], directory: str, max_shar
         cur_bytes += nb
     shards.append(cur)
     if len(shards) == 1:
-        save_file(shards[0], os.path.join(directory, WEIGHTS_NAME), metadata={"format": "pt"})
+        save_file(shards[0], os.path.join(directory, weights_name), metadata={"format": "pt"})
         return
     weight_map, total = {}, 0
     for i, sh in enumerate(shards):
-        fn = f"diffusion_pytorch_model-{i + 1:05d}-of-{len(shards):05d}.safetensors"
+        fn = f"{stem}-{i + 1:05d}-of-{len(shards):05d}.safetensors"
         save_file(sh, os.path.join(directory, fn), metadata={"format": "pt"})
         for k, v in sh.items():
             weight_map[k] = fn
             total += v.numel() * v.element_size()
-    with open(os.path.join(directory, INDEX_NAME), "w", encoding="utf-8") as f:
+    with open(os.path.join(directory, index_name), "w", encoding="utf-8") as f:
         json.dump({"metadata": {"total_size": total}, "weight_map": weight_map}, f, indent=2)

@@ -1347,7 +1347,8 @@ class CogVideoXImageToVideoPipelineTraj:
     output_type='pil' | 'latent' | 'pt' | 'np')`` / ``.scheduler`` / ``.vae`` / ``.text_encoder`` / ``.transformer``.
 
     Built here (MI355X): ``prepare_latents`` (:1115-1225), the denoise loop (:1402-1473) and - SURVEY §8(f) rank 1 - the VAE
-    (``orv_amd.vae.AutoencoderKLCogVideoX``, parity unpinned).  T5 is outside this build.  The pipeline DELEGATES to whatever
+    (``orv_amd.vae.AutoencoderKLCogVideoX``, parity unpinned) and the T5 text encoder (``orv_amd.t5.T5EncoderModel``); the tokenizer
+    is outside this build.  The pipeline DELEGATES to whatever
     ``vae`` / ``text_encoder`` / ``tokenizer`` objects it holds with exactly the calls the reference and its diffusers base
     class make (``vae.encode(x).latent_dist.sample(generator)``, ``vae.decode(z).sample``, ``tokenizer(prompt,
     padding='max_length', ...)``, ``text_encoder(ids)[0]``), so diffusers' own ``AutoencoderKLCogVideoX`` and transformers'
@@ -1398,8 +1399,8 @@ class CogVideoXImageToVideoPipelineTraj:
         or vanilla CogVideoX weights), ``scheduler/scheduler_config.json`` into this package's scheduler of the recorded
         class.  Components passed as keyword arguments win (inference_control_to_video.py:80-84 passes ``transformer=``).
         A ``vae/`` folder is loaded into ``orv_amd.vae.AutoencoderKLCogVideoX`` (diffusers' key names); a T5 under
-        ``text_encoder/`` + ``tokenizer/`` is loaded through ``transformers`` when that package is importable; otherwise supply
-        the objects."""
+        ``text_encoder/`` + ``tokenizer/`` is loaded through ``transformers`` when that package is importable; without it
+        ``text_encoder/`` goes into ``orv_amd.t5.T5EncoderModel`` and the tokenizer has to be supplied."""
         path = str(pretrained_model_name_or_path)
         index = {}
         ipath = os.path.join(path, cls.config_name)
@@ -1428,9 +1429,17 @@ class CogVideoXImageToVideoPipelineTraj:
         if text_encoder is None and os.path.isdir(os.path.join(path, "text_encoder")):
             try:
                 from transformers import T5EncoderModel
-                text_encoder = T5EncoderModel.from_pretrained(path, subfolder="text_encoder", torch_dtype=torch_dtype)
-            except Exception:            # absent package / weights: stays None, prompt= then asks for prompt_embeds
-                text_encoder = None
+            except Exception:            # package absent: the encoder of this library (orv_amd.t5, transformers' checkpoint layout)
+                from .t5 import T5EncoderModel
+                try:
+                    text_encoder = T5EncoderModel.from_pretrained(path, subfolder="text_encoder", torch_dtype=torch_dtype)
+                except Exception:        # absent / foreign weights or an unsupported config: None, as in the branch below
+                    text_encoder = None
+            else:
+                try:
+                    text_encoder = T5EncoderModel.from_pretrained(path, subfolder="text_encoder", torch_dtype=torch_dtype)
+                except Exception:        # absent weights: stays None, prompt= then asks for prompt_embeds
+                    text_encoder = None
         if tokenizer is None and os.path.isdir(os.path.join(path, "tokenizer")):
             try:
                 from transformers import T5Tokenizer
@@ -1487,9 +1496,10 @@ class CogVideoXImageToVideoPipelineTraj:
     # ---- text side: delegate to the attached T5 (diffusers CogVideoXPipeline.encode_prompt / _get_t5_prompt_embeds) ----
     def _get_t5_prompt_embeds(self, prompt, num_videos_per_prompt=1, max_sequence_length=226, device=None, dtype=None):
         if self.tokenizer is None or self.text_encoder is None:
-            raise NotImplementedError("prompt= needs the pipeline's `tokenizer` and `text_encoder` (T5) objects; they are not "
-                                      "built here (SURVEY §8f): attach them or pass prompt_embeds (the reference's dataset "
-                                      "caches them, dataset.py:1056-1059)")
+            raise NotImplementedError("prompt= needs the pipeline's `tokenizer` and `text_encoder` (T5) objects: attach a tokenizer "
+                                      "(transformers' T5Tokenizer or any callable of its call shape; not built here) and "
+                                      "text_encoder=orv_amd.t5.T5EncoderModel.from_pretrained(path, subfolder='text_encoder'), or pass "
+                                      "prompt_embeds (the reference's dataset caches them, dataset.py:1056-1059)")
         prompt = [prompt] if isinstance(prompt, str) else list(prompt)
         text_inputs = self.tokenizer(prompt, padding="max_length", max_length=max_sequence_length, truncation=True,
                                      add_special_tokens=True, return_tensors="pt")

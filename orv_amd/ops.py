@@ -672,3 +672,37 @@ def vae_norm_apply(x, out, sums, gamma, beta, zy, zb, B, T, H, W, C, G, Tz, hz, 
     check(lib().orv_vae_norm_apply(_p(x), _p(out), _p(sums), _p(gamma), _p(beta), _p(zy), _p(zb), B, T, H, W, C, G, Tz, hz, wz,
                                    float(eps), int(bool(silu)), int(out_lead), _stream()), "orv_vae_norm_apply")
     return out
+
+
+# ---- T5 text encoder (t5.hip) ----
+def t5_attention_max_seq() -> int:
+    """Longest sequence ``t5_attention_fwd`` takes."""
+    return int(lib().orv_t5_attention_max_seq())
+
+
+def t5_attention_fwd(qkv, bias_rel, out, B, S, H, ld_qkv=None, ld_out=None):
+    """T5 self-attention: ``out = softmax(q k^T + bias) v`` with no score scale; ``qkv`` bf16 [B S, 3 H 64] packed as ``attention_fwd`` reads it,
+    ``bias_rel`` fp32 [H, 2S - 1] (entry j - i + S - 1: query i, key j), ``out`` bf16 [B S, H 64]."""
+    _need(qkv, BF16, "qkv"), _need(out, BF16, "out"), _need(bias_rel, torch.float32, "bias_rel")
+    if not bias_rel.is_contiguous() or bias_rel.numel() != H * (2 * S - 1):
+        raise ValueError(f"t5_attention_fwd: bias_rel must be contiguous [H, 2S - 1] = [{H}, {2 * S - 1}] (got {tuple(bias_rel.shape)})")
+    with _timed(("t5_attention", B, S, H)):
+        check(lib().orv_t5_attention_fwd(_p(qkv), ld_qkv or 3 * H * 64, _p(bias_rel), _p(out), ld_out or H * 64, B, S, H, _stream()),
+              "orv_t5_attention_fwd")
+    return out
+
+
+def t5_rmsnorm(x, w, y, M, D, eps, ldx=None, ldy=None):
+    """``y = w * bf16(x * rsqrt(mean(x^2) + eps))`` over rows of bf16 [M, D] (T5LayerNorm: no mean subtraction, no bias)."""
+    _need(x, BF16, "x"), _need(w, BF16, "w"), _need(y, BF16, "y")
+    if w.numel() != D or not w.is_contiguous():
+        raise ValueError(f"t5_rmsnorm: w must hold {D} contiguous elements")
+    check(lib().orv_t5_rmsnorm(_p(x), ldx or D, _p(w), _p(y), ldy or D, M, D, float(eps), _stream()), "orv_t5_rmsnorm")
+    return y
+
+
+def geglu(h, out, M, F, ldh=None, ldo=None):
+    """``out[:, f] = gelu_tanh(h[:, f]) * h[:, F + f]`` (bf16 [M, 2F] -> bf16 [M, F], fp32 inside, one rounding)."""
+    _need(h, BF16, "h"), _need(out, BF16, "out")
+    check(lib().orv_geglu(_p(h), ldh or 2 * F, _p(out), ldo or F, M, F, _stream()), "orv_geglu")
+    return out
