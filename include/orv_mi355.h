@@ -312,6 +312,30 @@ int orv_adamw_flat_s8(void* p, const void* g, unsigned char* m8, unsigned char* 
  * (exact).  format 0 = first moment (e4m3fn), 1 = second moment (e5m2); n % 256 == 0. */
 int orv_state8_quantize(const float* x, unsigned char* q, unsigned char* exps, long n, int format, unsigned seed, int step, void* stream);
 int orv_state8_dequantize(const unsigned char* q, const unsigned char* exps, float* x, long n, int format, void* stream);
+/* Fused Prodigy (FusedProdigy; the rule and its operation order are stated in orv_amd/csrc/optim_prodigy.hip) on the flat
+ * layout of orv_adamw_flat_ex mode 1: p bf16[n] + lo int16[n] are the split fp32 master, g bf16[>= n] the gradient, m / v / s fp32[n] the
+ * per-element state, p0 bf16[n] the weight at a parameter's first update, seg_start / seg_active / seg_step as in orv_adamw_flat_ex
+ * (seg_step REQUIRED: a segment whose count is 1 captures p0 = the bf16 part of its master).  One step is these three calls on one stream;
+ * no scalar leaves the device.  state is fp64[8] on the device: d, d_max, d_numerator, d_denom, d_hat, k (completed updates), the dlr of
+ * the running step, the skip flag; a fresh optimizer holds {d0, d0, 0, 0, 0, 0, 0, 0}.
+ *   orv_prodigy_moments    - updates m, v, s of the active segments from the OLD d and k (dlr = d lr bc is computed in the kernel) and stores
+ *                            one fp64 pair per 2048-element chunk, partials[2 c] = sum (d / d0) dlr g (p0 - w), partials[2 c + 1] = sum |s|
+ *                            (zeros for the chunks of an inactive segment).  No atomics: the result depends on the inputs only.
+ *   orv_prodigy_recurrence - one workgroup adds the nchunks pairs in fp64 and advances d, d_max, d_numerator, d_hat, k; when the denominator
+ *                            is 0 (nothing ever had a non-zero gradient) it leaves them as they are and raises the skip flag.
+ *   orv_prodigy_update     - w -= (wd dlr) w (decoupled decay) ; w -= dlr m / (sqrt(v) + d eps) on the master with the NEW d, stored by the
+ *                            rounding rule of orv_adamw_flat_ex mode 1; does nothing when the skip flag is set.
+ * Inactive segments keep every byte of p, lo, m, v, s and p0.  n % 2048 != 0, eps <= 0, d0 <= 0 or a null buffer (clip_coef may be NULL)
+ * return non-zero with an orv_last_error message before anything is launched. */
+int orv_prodigy_moments(const void* p, const void* lo, const void* g, void* p0, float* m, float* v, float* s, long n,
+                        const long* seg_start, const unsigned char* seg_active, const int* seg_step, int nseg, const double* state,
+                        double* partials, float lr, float beta1, float beta2, float beta3, float weight_decay, int decouple,
+                        int safeguard_warmup, int use_bias_correction, double d0, const float* clip_coef, void* stream);
+int orv_prodigy_recurrence(double* state, const double* partials, long nchunks, float lr, float beta1, float beta2, float beta3,
+                           int use_bias_correction, double d0, double d_coef, double growth_rate, void* stream);
+int orv_prodigy_update(void* p, void* lo, const float* m, const float* v, long n, const long* seg_start,
+                       const unsigned char* seg_active, int nseg, const double* state, float eps, float weight_decay, int decouple,
+                       void* stream);
 /* dst_ptr[s][j] = bf16(src[src_off[s] + j]), j < len[s], for nseg segments (src_off / dst_ptr / len are DEVICE arrays; dst_ptr holds
  * device addresses of bf16 storage; max_len = max len[s]): the small fp32-accumulated parameter gradients go from the backward's
  * accumulator arena into the fused optimizer's flat gradient buffer in one launch (the reference leaves this to autograd's

@@ -19,3 +19,11 @@ def install(verbose: bool = False):
     in ``sys.modules`` so the reference's entry points run unchanged - see ``orv_amd/dropin.py``."""
     from .dropin import install as _install
     return _install(verbose=verbose)
+
+
+def __getattr__(name):
+    # the optimizer surface of the train scripts, resolved on first use (importing the package stays free of torch)
+    if name in ("FusedProdigy", "get_optimizer"):
+        from . import optim
+        return getattr(optim, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

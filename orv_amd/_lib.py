@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_long, c_uint, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ORV_LIB: another build of the same library (developer A/B runs: tools/*.sh); the default is the in-tree build
@@ -111,6 +111,12 @@ SIGNATURES = {
                                   c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_uint, c_void_p]),
     "orv_state8_quantize": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_uint, c_int, c_void_p]),
     "orv_state8_dequantize": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]),
+    "orv_prodigy_moments": (c_int, [c_void_p] * 7 + [c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float,
+                                    c_float, c_float, c_float, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
+    "orv_prodigy_recurrence": (c_int, [c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_int, c_double, c_double, c_double,
+                                       c_void_p]),
+    "orv_prodigy_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float,
+                                   c_int, c_void_p]),
     "orv_scatter_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "orv_sumsq": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "orv_head_transpose": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

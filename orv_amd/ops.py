@@ -540,6 +540,61 @@ def adamw_flat_ex(p, g, m, v, seg_start, seg_active, lr, beta1, beta2, eps, weig
                                   int(step), _p(clip_coef), _p(lo), int(mode), int(seed) & 0xFFFFFFFF, _stream()), "orv_adamw_flat_ex")
 
 
+PRODIGY_STATE = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k", "dlr", "skip")      # the fp64[8] device state of orv_prodigy_*
+
+
+def _need_prodigy_layout(what, p, lo, m, v, seg_start, seg_active, state, extra=()):
+    _need(p, BF16, "p"), _need(lo, torch.int16, "lo"), _need(m, torch.float32, "m"), _need(v, torch.float32, "v")
+    _need(seg_start, torch.int64, "seg_start"), _need(seg_active, torch.uint8, "seg_active"), _need(state, torch.float64, "state")
+    for name, t in (("p", p), ("lo", lo), ("m", m), ("v", v), ("seg_start", seg_start), ("seg_active", seg_active), ("state", state)) + tuple(extra):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+    n = p.numel()
+    if (lo.numel() != n or m.numel() != n or v.numel() != n or seg_start.numel() != seg_active.numel() + 1
+            or state.numel() != len(PRODIGY_STATE)):
+        raise RuntimeError(f"orv_amd.ops: {what} buffers do not share one flat layout (state: fp64[{len(PRODIGY_STATE)}])")
+
+
+def prodigy_moments(p, lo, g, p0, m, v, s, seg_start, seg_active, seg_step, state, partials, lr, beta1, beta2, beta3, weight_decay=0.0,
+                    decouple=True, safeguard_warmup=False, use_bias_correction=False, d0=1e-6, clip_coef=None):
+    """Launch 1 of a fused Prodigy step (``orv_prodigy_moments``): the moments ``m``, ``v``, ``s`` of the active segments from the OLD ``d`` and
+    ``k`` in ``state`` (fp64[8], ``PRODIGY_STATE``), ``p0`` (bf16, the weight at a parameter's first update) for segments whose ``seg_step`` is
+    1, and one fp64 (numerator, denominator) pair per 2048-element chunk in ``partials`` (fp64[2 * chunks])."""
+    _need_prodigy_layout("prodigy_moments", p, lo, m, v, seg_start, seg_active, state,
+                         (("g", g), ("p0", p0), ("s", s), ("seg_step", seg_step), ("partials", partials)))
+    _need(g, BF16, "g"), _need(p0, BF16, "p0"), _need(s, torch.float32, "s"), _need(seg_step, torch.int32, "seg_step")
+    _need(partials, torch.float64, "partials")
+    if clip_coef is not None:
+        _need(clip_coef, torch.float32, "clip_coef")
+    n = p.numel()
+    if g.numel() < n or p0.numel() != n or s.numel() != n or seg_step.numel() != seg_active.numel() or partials.numel() * 1024 != n:
+        raise RuntimeError("orv_amd.ops: prodigy_moments buffers do not share one flat layout (partials: one fp64 pair per 2048 elements)")
+    check(lib().orv_prodigy_moments(_p(p), _p(lo), _p(g), _p(p0), _p(m), _p(v), _p(s), n, _p(seg_start), _p(seg_active), _p(seg_step),
+                                    seg_active.numel(), _p(state), _p(partials), float(lr), float(beta1), float(beta2), float(beta3),
+                                    float(weight_decay), int(bool(decouple)), int(bool(safeguard_warmup)), int(bool(use_bias_correction)),
+                                    float(d0), _p(clip_coef), _stream()), "orv_prodigy_moments")
+
+
+def prodigy_recurrence(state, partials, lr, beta1, beta2, beta3, use_bias_correction=False, d0=1e-6, d_coef=1.0, growth_rate=float("inf")):
+    """Launch 2 (``orv_prodigy_recurrence``): adds the pairs of ``partials`` in fp64 and advances ``state`` (d, d_max, d_numerator, d_hat, k),
+    or raises its skip flag when the denominator is 0."""
+    _need(state, torch.float64, "state"), _need(partials, torch.float64, "partials")
+    if (not state.is_contiguous() or not partials.is_contiguous() or state.numel() != len(PRODIGY_STATE) or partials.numel() < 2
+            or partials.numel() % 2):
+        raise RuntimeError(f"orv_amd.ops: prodigy_recurrence wants contiguous state fp64[{len(PRODIGY_STATE)}] and partials fp64[2 * chunks]")
+    check(lib().orv_prodigy_recurrence(_p(state), _p(partials), partials.numel() // 2, float(lr), float(beta1), float(beta2), float(beta3),
+                                       int(bool(use_bias_correction)), float(d0), float(d_coef), float(growth_rate), _stream()),
+          "orv_prodigy_recurrence")
+
+
+def prodigy_update(p, lo, m, v, seg_start, seg_active, state, eps, weight_decay=0.0, decouple=True):
+    """Launch 3 (``orv_prodigy_update``): the weight update on the split fp32 master (``p`` bf16 + ``lo`` int16, the format of
+    ``adamw_flat_ex`` mode 1) with the NEW ``d`` and this step's ``dlr`` from ``state``; nothing when the skip flag is set."""
+    _need_prodigy_layout("prodigy_update", p, lo, m, v, seg_start, seg_active, state)
+    check(lib().orv_prodigy_update(_p(p), _p(lo), _p(m), _p(v), p.numel(), _p(seg_start), _p(seg_active), seg_active.numel(), _p(state),
+                                   float(eps), float(weight_decay), int(bool(decouple)), _stream()), "orv_prodigy_update")
+
+
 STATE8_FORMATS = {"m": 0, "v": 1}          # first moment: e4m3fn, second moment: e5m2 (orv_amd/csrc/optim_s8.hip)
 
 

@@ -21,7 +21,10 @@ to bf16 with a 16-bit random offset drawn from a hash of (seed, step count, flat
 State precision (``state_precision``): the default ``"fp32"`` keeps both moments in fp32 (8 bytes per element).  ``"fp8"`` keeps
 them as block-scaled fp8 - one byte per element (first moment e4m3fn, second e5m2) plus one scale byte per block of 256, 2 + 2/256 bytes per
 element - rounded stochastically with offsets from the same kind of hash (``seed`` is shared with the stochastic weight mode), so all ranks hold
-identical state.  It is orthogonal to ``param_precision``; the format is defined in ``orv_amd/csrc/optim_s8.hip``."""
+identical state.  It is orthogonal to ``param_precision``; the format is defined in ``orv_amd/csrc/optim_s8.hip``.
+
+``FusedProdigy`` is the learning-rate-free Prodigy update on the same storage, ``get_optimizer`` the reference's factory
+(``train.optimizer.type: adamw | adam | prodigy``) over both classes."""
 from __future__ import annotations
 
 from typing import Iterable, List, Optional
@@ -39,6 +42,8 @@ _AR_CHUNK = 128 * 1024 * 1024   # bf16 elements per all-reduce call (256 MB: lar
 
 
 class FusedAdamW:
+    _checkpoint_kind = "adamw"
+
     def __init__(self, params: Iterable[torch.nn.Parameter], lr=1e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-3,
                  max_grad_norm: float = 1.0, param_precision: str = "bf16", seed: int = 0, state_precision: str = "fp32"):
         if param_precision not in PARAM_PRECISIONS:
@@ -234,6 +239,12 @@ class FusedAdamW:
             clip = clip / world
         self.step_count += 1
         f["seg_step"].add_(f["active"].to(torch.int32))          # per-parameter step counts (torch.optim.AdamW state["step"])
+        self._launch_update(f, clip)
+        _state.bump_weights_epoch()      # parameters changed without a tensor._version bump: drop derived-weight caches
+        return float(norm.item())
+
+    def _launch_update(self, f, clip):
+        """The update kernel(s) of one step on the flat buffers ``f``; ``clip`` is the device-side coefficient (1 / world folded in)."""
         if self.state_precision == "fp8":
             if "lo" in f:
                 self._drop_stale_param_lo()
@@ -249,8 +260,6 @@ class FusedAdamW:
             ops.adamw_flat_ex(f["p"], f["g"], f["m"], f["v"], f["seg_start"], f["active"], self.param_groups[0]["lr"], self.betas[0],
                               self.betas[1], self.eps, self.weight_decay, self.step_count, clip, seg_step=f["seg_step"],
                               lo=f.get("lo"), mode=ops.ADAMW_MODES[self.param_precision], seed=self.seed)
-        _state.bump_weights_epoch()      # parameters changed without a tensor._version bump: drop derived-weight caches
-        return float(norm.item())
 
     # ---- fp32 masters (param_precision="split_fp32") ----
     def _drop_stale_param_lo(self):
@@ -332,6 +341,9 @@ class FusedAdamW:
         return sd
 
     def load_state_dict(self, sd):
+        if sd.get("optimizer") not in (None, self._checkpoint_kind):        # FusedAdamW's own checkpoints carry no such key
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the checkpoint was written by the {sd['optimizer']!r} optimizer; its moments "
+                             "have another meaning (Prodigy's carry a factor d) and are not taken over")
         layout = [int(p.numel()) for p in self.params]
         if sd.get("numels") is not None and list(sd["numels"]) != layout:
             if sorted(sd["numels"]) == sorted(layout):
@@ -380,6 +392,175 @@ class FusedAdamW:
                 self._flat["seg_step"].copy_(sd["seg_step"])
             else:                           # checkpoints written before per-parameter counts existed
                 self._flat["seg_step"].fill_(self.step_count)
+
+
+class FusedProdigy(FusedAdamW):
+    """Prodigy, the learning-rate-free optimizer of the CogVideoX LoRA recipes (``train.optimizer.type: prodigy``; the reference's orv/utils.py:112-134),
+    fused on the flat storage of ``FusedAdamW``: same flat bf16 gradient buffer, device-side clip coefficient, usage mask, overlapped gradient
+    exchange and per-parameter skip; only the update differs.  The rule restates ``prodigyopt`` 1.0's ``Prodigy.step`` from
+    memory (unpinned: the package is not available to compare against; one parameter group, no ``slice_p`` / ``fsdp_in_use``) and is written
+    out in ``orv_amd/csrc/optim_prodigy.hip``.  A step is three stream-ordered launches - moments and per-chunk partial sums, the scalar
+    recurrence of the step-size estimate ``d``, the weight update - and every scalar (``d``, ``d_max``, ``d_numerator``, ``k``) lives in a
+    small fp64 array on the device: the host reads nothing inside a step.  Under data parallel every rank holds the same summed gradient and
+    therefore computes the same ``d``; no collective is added.
+
+    The weights are ALWAYS the exact split fp32 master of ``FusedAdamW(param_precision="split_fp32")``: the first updates have the size of
+    ``d0`` (1e-6), far below half a bf16 step of any weight, so on bf16 weights ``p0 - p`` stays exactly 0, the numerator of the estimate
+    stays 0 and ``d`` never leaves ``d0``.  ``p0``, the weight at a parameter's first update, is stored as bf16: at that moment the low half
+    of a parameter this optimizer never updated is zero and the bf16 value is the master exactly.  If a low half is not zero then (a loaded
+    checkpoint of another optimizer's masters) nothing is zeroed or refused: ``p0`` is the bf16 part of the master.
+
+    ``lr`` multiplies the estimate (keep it at 1.0; schedules poke ``param_groups[0]["lr"]``, read at every step).  ``d``, ``d_max``,
+    ``d_hat``, ``k``, ``dlr`` are host reads on demand, for logging."""
+
+    _checkpoint_kind = "prodigy"      # state_dict()["optimizer"]
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr=1.0, betas=(0.9, 0.999), beta3: Optional[float] = None, eps=1e-8,
+                 weight_decay=0.0, decouple: bool = True, use_bias_correction: bool = False, safeguard_warmup: bool = False, d0=1e-6,
+                 d_coef=1.0, growth_rate=float("inf"), max_grad_norm: float = 1.0, param_precision: str = "split_fp32",
+                 state_precision: str = "fp32"):
+        if param_precision in ("bf16", "stochastic"):
+            raise ValueError(f"FusedProdigy: param_precision={param_precision!r} cannot work: the first updates have the size of d0 = {d0:g}, "
+                             "far below half a bf16 step of the weights, so they vanish in bf16, p0 - p stays 0 and d never grows "
+                             "(supported: 'split_fp32', the exact fp32 master)")
+        if param_precision != "split_fp32":
+            raise ValueError(f"FusedProdigy: unknown param_precision {param_precision!r} (supported: 'split_fp32')")
+        if state_precision != "fp32":
+            raise ValueError(f"FusedProdigy: state_precision={state_precision!r} is not built for Prodigy (supported: 'fp32')")
+        if not eps > 0:
+            raise ValueError(f"FusedProdigy: eps={eps} must be greater than 0 (an element whose second moment is 0 divides by d * eps)")
+        if not d0 > 0:
+            raise ValueError(f"FusedProdigy: d0={d0} must be greater than 0")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                         param_precision="split_fp32", state_precision="fp32")
+        self.beta3 = float(betas[1]) ** 0.5 if beta3 is None else float(beta3)
+        self.decouple, self.use_bias_correction, self.safeguard_warmup = bool(decouple), bool(use_bias_correction), bool(safeguard_warmup)
+        self.d0, self.d_coef, self.growth_rate = float(d0), float(d_coef), float(growth_rate)
+
+    def _build(self):
+        super()._build()
+        f = self._flat
+        dev, total = f["p"].device, f["p"].numel()
+        f.update(s=torch.zeros(total, dtype=torch.float32, device=dev), p0=torch.zeros(total, dtype=torch.bfloat16, device=dev),
+                 partials=torch.zeros(2 * (total // _SEG), dtype=torch.float64, device=dev),     # one (numerator, denominator) pair per chunk
+                 pstate=torch.tensor([self.d0, self.d0] + [0.0] * (len(ops.PRODIGY_STATE) - 2), dtype=torch.float64, device=dev))
+
+    def _launch_update(self, f, clip):
+        self._drop_stale_param_lo()
+        lr, (b1, b2) = self.param_groups[0]["lr"], self.betas
+        ops.prodigy_moments(f["p"], f["lo"], f["g"], f["p0"], f["m"], f["v"], f["s"], f["seg_start"], f["active"], f["seg_step"], f["pstate"],
+                            f["partials"], lr, b1, b2, self.beta3, self.weight_decay, self.decouple, self.safeguard_warmup,
+                            self.use_bias_correction, self.d0, clip)
+        ops.prodigy_recurrence(f["pstate"], f["partials"], lr, b1, b2, self.beta3, self.use_bias_correction, self.d0, self.d_coef,
+                               self.growth_rate)
+        ops.prodigy_update(f["p"], f["lo"], f["m"], f["v"], f["seg_start"], f["active"], f["pstate"], self.eps, self.weight_decay,
+                           self.decouple)
+
+    # ---- the step-size estimate (host reads, for logging only) ----
+    def _scalar(self, name: str) -> float:
+        if self._flat is None:
+            return {"d": self.d0, "d_max": self.d0}.get(name, 0.0)
+        return float(self._flat["pstate"][ops.PRODIGY_STATE.index(name)].item())
+
+    d = property(lambda self: self._scalar("d"), doc="the step-size estimate after the last step")
+    d_max = property(lambda self: self._scalar("d_max"))
+    d_hat = property(lambda self: self._scalar("d_hat"), doc="the last raw estimate d_coef * numerator / denominator")
+    k = property(lambda self: int(self._scalar("k")), doc="completed updates (a step whose denominator was 0 does not count)")
+    dlr = property(lambda self: self._scalar("dlr"), doc="d * lr * bias correction the last step ran with")
+
+    @torch.no_grad()
+    def prodigy_state(self):
+        """``(s, p0)``: per-parameter copies (fp32 / bf16, shaped like the parameters, ``self.params`` order) of the estimate's running sum and
+        of the weight at the first update.  For tests and exports."""
+        if self._flat is None:
+            self._build()
+        f = self._flat
+        cut = lambda x: [x[o:o + p.numel()].view(p.shape).clone() for p, o in zip(self.params, f["offs"])]
+        return cut(f["s"]), cut(f["p0"])
+
+    # ---- checkpointing ----
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["optimizer"] = "prodigy"
+        for key, buf in (("prodigy_s", "s"), ("prodigy_p0", "p0"), ("prodigy_state", "pstate")):
+            sd[key] = None if self._flat is None else self._flat[buf]
+        return sd
+
+    def load_state_dict(self, sd):
+        if sd.get("exp_avg8") is not None:
+            raise ValueError("FusedProdigy.load_state_dict: the checkpoint holds fp8 moments; Prodigy keeps fp32 state only")
+        super().load_state_dict(sd)
+        if sd.get("prodigy_state") is None:
+            if sd.get("exp_avg") is not None:
+                raise ValueError("FusedProdigy.load_state_dict: the checkpoint has AdamW moments but no Prodigy state (s, p0, d): it was "
+                                 "written by FusedAdamW; its moments have another meaning (Prodigy's carry a factor d)")
+            return
+        if self._flat is None:
+            self._build()
+        f = self._flat
+        for key, buf in (("prodigy_s", "s"), ("prodigy_p0", "p0"), ("prodigy_state", "pstate")):
+            if sd.get(key) is None or sd[key].numel() != f[buf].numel():
+                raise ValueError(f"FusedProdigy.load_state_dict: {key} does not match the flat layout")
+            f[buf].copy_(sd[key])
+
+
+_OPTIMIZERS = ("adam (weight_decay == 0 only)", "adamw", "prodigy")
+
+
+def get_optimizer(params_to_optimize, optimizer_name: str = "adam", learning_rate: float = 1e-3, beta1: float = 0.9, beta2: float = 0.95,
+                  beta3: float = 0.98, epsilon: float = 1e-8, weight_decay: float = 1e-4, prodigy_decouple: bool = False,
+                  prodigy_use_bias_correction: bool = False, prodigy_safeguard_warmup: bool = False, use_8bit: bool = False,
+                  use_4bit: bool = False, use_torchao: bool = False, use_deepspeed: bool = False, use_cpu_offload_optimizer: bool = False,
+                  offload_gradients: bool = False, max_grad_norm: float = 1.0, **fused_kwargs):
+    """The reference's optimizer factory (its orv/utils.py:16-163, driven by ``train.optimizer.*`` of config/base_train.yaml:143-158):
+    same argument names, order and defaults; ``max_grad_norm`` and ``**fused_kwargs`` are this project's own, because the fused optimizers
+    clip inside their step.  ``fused_kwargs`` are keyword arguments of the chosen class - ``param_precision=``, ``state_precision=`` and
+    ``seed=`` for ``FusedAdamW``; ``d0=``, ``d_coef=``, ``growth_rate=`` for ``FusedProdigy`` - and any other name is refused with the
+    accepted set.  ``adamw`` -> ``FusedAdamW`` (``use_8bit``: fp8
+    moments), ``adam`` -> the same where Adam and AdamW coincide (``weight_decay == 0``), ``prodigy`` -> ``FusedProdigy``; an unknown name falls
+    back to ``adamw`` with a warning as the reference does.  CAME, 4-bit / torchao / DeepSpeed / CPU-offloaded optimizers are not built and
+    are refused.  ``params_to_optimize``: an iterable of parameters, or the reference's list of one ``{"params": ..., "lr": ...}`` dict (its
+    ``lr`` wins over ``learning_rate``, as in torch)."""
+    import warnings
+    supported = f"supported: optimizer_name in {', '.join(_OPTIMIZERS)}; use_8bit with adam / adamw (fp8 moments)"
+    name = str(optimizer_name).lower()
+    for flag, on in (("use_deepspeed", use_deepspeed), ("use_4bit", use_4bit), ("use_torchao", use_torchao),
+                     ("use_cpu_offload_optimizer", use_cpu_offload_optimizer)):
+        if on:
+            raise ValueError(f"get_optimizer: {flag}=True is not built here ({supported})")
+    if name not in ("adam", "adamw", "prodigy", "came"):
+        warnings.warn(f"get_optimizer: optimizer_name={name!r} is not known ({supported}); falling back to 'adamw'")
+        name = "adamw"
+    if name == "came":
+        raise ValueError(f"get_optimizer: CAME is not built here ({supported})")
+    if use_8bit and name not in ("adam", "adamw"):
+        raise ValueError(f"get_optimizer: use_8bit=True goes with adam / adamw only, not with {name!r} ({supported})")
+    params = list(params_to_optimize)
+    if params and isinstance(params[0], dict):
+        if len(params) != 1:
+            raise ValueError(f"get_optimizer: {len(params)} parameter groups; the fused optimizers keep one flat buffer, i.e. one group")
+        learning_rate = params[0].get("lr", learning_rate)
+        params = list(params[0]["params"])
+    cls = FusedProdigy if name == "prodigy" else FusedAdamW
+    own = {"prodigy": ("d0", "d_coef", "growth_rate", "param_precision", "state_precision")}.get(name, ("param_precision", "state_precision", "seed"))
+    unknown = sorted(set(fused_kwargs) - set(own))
+    if unknown:
+        raise ValueError(f"get_optimizer: {cls.__name__} takes no {', '.join(unknown)} (accepted beside the reference's arguments: {', '.join(own)})")
+    if name == "prodigy":
+        if learning_rate <= 0.1:
+            warnings.warn(f"get_optimizer: learning_rate={learning_rate:g} is small for prodigy, whose lr multiplies its own step-size estimate; "
+                          "values near 1.0 are the usual choice")
+        return FusedProdigy(params, lr=learning_rate, betas=(beta1, beta2), beta3=beta3, eps=epsilon, weight_decay=weight_decay,
+                            decouple=prodigy_decouple, use_bias_correction=prodigy_use_bias_correction,
+                            safeguard_warmup=prodigy_safeguard_warmup, max_grad_norm=max_grad_norm, **fused_kwargs)
+    if name == "adam" and weight_decay != 0:
+        raise ValueError(f"get_optimizer: coupled weight decay (torch.optim.Adam with weight_decay={weight_decay}) is not built; Adam is "
+                         f"provided only at weight_decay == 0, where it coincides with AdamW - use optimizer_name='adamw' for decoupled "
+                         f"decay ({supported})")
+    if use_8bit:
+        fused_kwargs.setdefault("state_precision", "fp8")
+    return FusedAdamW(params, lr=learning_rate, betas=(beta1, beta2), eps=epsilon, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                      **fused_kwargs)
 
 
 # ---- learning-rate schedules of the train tail (train_cogvideox_control_to_video_sft.py:740-747, :1107; base_train.yaml:160-164) ----
