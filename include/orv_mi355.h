@@ -482,6 +482,41 @@ int orv_vae_norm_apply(const void* x, void* out, const float* sums, const void* 
 int orv_vae_blend(const void* a, void* b, int outer, int Ha, int Wa, int Hb, int Wb, int C, int extent, int horizontal,
                   void* stream);
 
+/* -- Gaussian rasterizer: ORV's depth / semantic conditioning renders ----------------------------------------------------------------
+ * Forward splatting of N 3-D Gaussians into colour [3,H,W], feature [F,H,W], depth [1,H,W] and alpha [1,H,W] planes, replacing the CUDA
+ * extension orv/ops/diff-gaussian-rasterization (Python surface diff_gaussian_rasterization/__init__.py:21-236) that
+ * orv/dataset/gs_render.py:97-171 calls once per frame and view from orv/dataset/prepare_dataset.py:2023-2235.  fp32 throughout,
+ * forward only, no atomics (bit-reproducible).  The arithmetic contract - near plane 0.01, 16x16 tiles, the radius and tile-rectangle
+ * rules, the blend thresholds 1/255 and 1e-4, the (depth, index) order - is written out in DESIGN.md section 12.  Matrices are
+ * row-major [4,4] device arrays in the row-vector convention of gs_render.py:128-130: viewmatrix = (world-to-camera)^T,
+ * projmatrix = viewmatrix @ P^T, a point maps as [p,1] @ M.  A render is four calls with two torch steps between them:
+ *   preprocess -> cumsum(tiles_touched) -> tile_keys -> stable sort of the keys -> tile_ranges (ranges zeroed first) -> render.
+ *
+ * Per Gaussian (replaces the extension's preprocessing stage behind gs_render.py:151-160): view-space depth, pixel centre xy [N,2],
+ * conic_opacity [N,4] = (A, B, C, opacity), radii [N] (0 = invisible), rect [N,4] = (x0, y0, x1, y1) in tiles, tiles_touched [N].
+ * N = 0 launches nothing. */
+int orv_gs_preprocess(const float* means3D, const float* scales, const float* rotations, const float* opacities,
+                      const float* viewmatrix, const float* projmatrix, int N, int H, int W, float tanfovx, float tanfovy,
+                      float scale_modifier, float* xy, float* conic_opacity, float* depth, int* radii, int* rect,
+                      int* tiles_touched, void* stream);
+/* One int64 key per (Gaussian, covered tile) pair (replaces the extension's key duplication stage behind gs_render.py:151-160):
+ * tile id (y * ceil(W/16) + x) in the high 32 bits, the fp32 bits of the view-space depth in the low 32; gaussian_idx [L] holds the
+ * Gaussian of each pair.  offsets [N] = inclusive prefix sum of tiles_touched (int64), L = offsets[N-1] < 2^31.  Pairs are laid out by
+ * ascending Gaussian index, so a stable sort of the keys breaks depth ties by index.  N = 0 or L = 0 launches nothing. */
+int orv_gs_tile_keys(const int* rect, const float* depth, const long* offsets, int N, int H, int W, long L, long* keys,
+                     int* gaussian_idx, void* stream);
+/* ranges [tiles, 2] = [start, end) of each tile's run in the sorted keys (replaces the extension's range identification stage behind
+ * gs_render.py:151-160).  The caller zeroes `ranges` first: a tile no Gaussian covers keeps (0, 0).  L = 0 launches nothing. */
+int orv_gs_tile_ranges(const long* sorted_keys, long L, int H, int W, int* ranges, void* stream);
+/* Per-tile front-to-back blend (replaces the extension's render stage behind gs_render.py:151-160; outputs in the order of
+ * diff_gaussian_rasterization/__init__.py:103): one 256-thread workgroup per tile, the tile's list point_list[start, end) staged through
+ * LDS in batches of 256 entries.  colors [N,3], features [N,F] with 0 <= F <= 16 (F = 0: no feature plane, features / out_feature may
+ * be NULL), bg [3] on the device.  color = sum + T * bg, feature and depth are plain sums, alpha = 1 - T.  With L = 0 the per-Gaussian
+ * arrays may be NULL and every pixel is background. */
+int orv_gs_render(const int* ranges, const int* point_list, long L, const float* xy, const float* conic_opacity,
+                  const float* depth, const float* colors, const float* features, int N, int F, const float* bg, int H, int W,
+                  float* out_color, float* out_feature, float* out_depth, float* out_alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,10 @@ SIGNATURES = {
     "orv_t5_attention_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "orv_t5_rmsnorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "orv_geglu": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "orv_gs_preprocess": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_float, c_float] + [c_void_p] * 7),
+    "orv_gs_tile_keys": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
+    "orv_gs_tile_ranges": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "orv_gs_render": (c_int, [c_void_p, c_void_p, c_long] + [c_void_p] * 5 + [c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5),
 }
 
 _lib = None

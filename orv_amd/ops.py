@@ -761,3 +761,86 @@ def geglu(h, out, M, F, ldh=None, ldo=None):
     _need(h, BF16, "h"), _need(out, BF16, "out")
     check(lib().orv_geglu(_p(h), ldh or 2 * F, _p(out), ldo or F, M, F, _stream()), "orv_geglu")
     return out
+
+
+# ---- Gaussian rasterizer (gs_render.hip) ----
+def _need_c(t, dtype, name):
+    if not t.is_contiguous():
+        raise ValueError(f"orv_amd.ops: `{name}` must be contiguous")
+    return _need(t, dtype, name)
+
+
+def _same_device(*named):
+    dev = named[0][0].device
+    for t, n in named:
+        if t.device != dev:
+            raise RuntimeError(f"orv_amd.ops: `{n}` is on {t.device} but `{named[0][1]}` is on {dev}; all operands of one call share a device")
+
+
+def gs_preprocess(means3D, scales, rotations, opacities, viewmatrix, projmatrix, H, W, tanfovx, tanfovy, scale_modifier):
+    """Project N Gaussians: -> (xy [N,2], conic_opacity [N,4], depth [N], radii [N] int32, rect [N,4] int32, tiles_touched [N] int32)."""
+    f32 = torch.float32
+    for t, n in ((means3D, "means3D"), (scales, "scales"), (rotations, "rotations"), (opacities, "opacities"), (viewmatrix, "viewmatrix"),
+                 (projmatrix, "projmatrix")):
+        _need_c(t, f32, n)
+    _same_device((means3D, "means3D"), (scales, "scales"), (rotations, "rotations"), (opacities, "opacities"), (viewmatrix, "viewmatrix"),
+                 (projmatrix, "projmatrix"))
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise ValueError(f"gs_preprocess: means3D must be [N,3] (got {tuple(means3D.shape)})")
+    N, dev = means3D.shape[0], means3D.device
+    if scales.numel() != 3 * N or rotations.numel() != 4 * N or opacities.numel() != N or viewmatrix.numel() != 16 or projmatrix.numel() != 16:
+        raise ValueError("gs_preprocess: means3D [N,3], scales [N,3], rotations [N,4], opacities [N,1], viewmatrix / projmatrix [4,4]")
+    xy, conic_op, depth = torch.empty(N, 2, dtype=f32, device=dev), torch.empty(N, 4, dtype=f32, device=dev), torch.empty(N, dtype=f32, device=dev)
+    radii, rect = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, 4, dtype=torch.int32, device=dev)
+    tiles = torch.empty(N, dtype=torch.int32, device=dev)
+    check(lib().orv_gs_preprocess(_p(means3D), _p(scales), _p(rotations), _p(opacities), _p(viewmatrix), _p(projmatrix), N, int(H), int(W),
+                                  float(tanfovx), float(tanfovy), float(scale_modifier), _p(xy), _p(conic_op), _p(depth), _p(radii), _p(rect),
+                                  _p(tiles), _stream()), "orv_gs_preprocess")
+    return xy, conic_op, depth, radii, rect, tiles
+
+
+def gs_tile_keys(rect, depth, offsets, H, W, L):
+    """-> (keys int64 [L], gaussian_idx int32 [L]); ``offsets`` = inclusive int64 prefix sum of tiles_touched, ``L`` its last entry."""
+    _need_c(rect, torch.int32, "rect"), _need_c(depth, torch.float32, "depth"), _need_c(offsets, torch.int64, "offsets")
+    _same_device((rect, "rect"), (depth, "depth"), (offsets, "offsets"))
+    if rect.dim() != 2 or rect.shape[1] != 4 or depth.numel() != rect.shape[0] or offsets.numel() != rect.shape[0]:
+        raise ValueError("gs_tile_keys: rect [N,4], depth [N], offsets [N]")
+    keys = torch.empty(L, dtype=torch.int64, device=rect.device)
+    idx = torch.empty(L, dtype=torch.int32, device=rect.device)
+    check(lib().orv_gs_tile_keys(_p(rect), _p(depth), _p(offsets), rect.shape[0], int(H), int(W), int(L), _p(keys), _p(idx), _stream()),
+          "orv_gs_tile_keys")
+    return keys, idx
+
+
+def gs_tile_ranges(sorted_keys, H, W):
+    """-> ranges int32 [tiles, 2]: [start, end) of each 16x16 tile's run in ``sorted_keys``; (0, 0) for a tile nothing covers."""
+    _need_c(sorted_keys, torch.int64, "sorted_keys")
+    ranges = torch.zeros(((H + 15) // 16) * ((W + 15) // 16), 2, dtype=torch.int32, device=sorted_keys.device)
+    check(lib().orv_gs_tile_ranges(_p(sorted_keys), sorted_keys.numel(), int(H), int(W), _p(ranges), _stream()), "orv_gs_tile_ranges")
+    return ranges
+
+
+def gs_render(ranges, point_list, xy, conic_opacity, depth, colors, features, bg, H, W):
+    """Blend every tile's list: -> (color [3,H,W], feature [F,H,W], depth [1,H,W], alpha [1,H,W]); ``features`` None or [N,0] = no feature plane."""
+    f32 = torch.float32
+    _need_c(ranges, torch.int32, "ranges"), _need_c(point_list, torch.int32, "point_list"), _need_c(bg, f32, "bg")
+    for t, n in ((xy, "xy"), (conic_opacity, "conic_opacity"), (depth, "depth"), (colors, "colors")):
+        _need_c(t, f32, n)
+    N = xy.shape[0]
+    F = 0 if features is None else int(features.shape[1])
+    if F:
+        _need_c(features, f32, "features")
+    _same_device((ranges, "ranges"), (point_list, "point_list"), (bg, "bg"), (xy, "xy"), (conic_opacity, "conic_opacity"), (depth, "depth"),
+                 (colors, "colors"), *(((features, "features"),) if F else ()))
+    if xy.numel() != 2 * N or conic_opacity.numel() != 4 * N or depth.numel() != N or ranges.numel() != 2 * ((H + 15) // 16) * ((W + 15) // 16):
+        raise ValueError("gs_render: xy [N,2], conic_opacity [N,4], depth [N], ranges [tiles,2]")
+    if colors.numel() != 3 * N or (F and features.shape[0] != N) or bg.numel() != 3:
+        raise ValueError("gs_render: colors [N,3], features [N,F], bg [3]")
+    dev = ranges.device
+    color, feat = torch.empty(3, H, W, dtype=f32, device=dev), torch.empty(F, H, W, dtype=f32, device=dev)
+    dep, alpha = torch.empty(1, H, W, dtype=f32, device=dev), torch.empty(1, H, W, dtype=f32, device=dev)
+    with _timed(("gs_render", N, F, H, W)):
+        check(lib().orv_gs_render(_p(ranges), _p(point_list), point_list.numel(), _p(xy), _p(conic_opacity), _p(depth), _p(colors),
+                                  _p(features) if F else None, N, F, _p(bg), int(H), int(W), _p(color), _p(feat) if F else None, _p(dep),
+                                  _p(alpha), _stream()), "orv_gs_render")
+    return color, feat, dep, alpha
