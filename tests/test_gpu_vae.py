@@ -65,6 +65,65 @@ def test_encode_matches_oracle(frames):
     assert torch.equal(s, dist.mean + dist.std * eps)
 
 
+# the real model's widths (4, 8 and 16 channels per group, every dispatch the real decoder / encoder takes), one resnet per block
+REAL_WIDTHS = dict(block_out_channels=(128, 256, 256, 512), layers_per_block=1)
+
+
+@pytest.mark.parametrize("frames", [3, 2])
+def test_decode_matches_oracle_at_the_real_widths(frames):
+    """3 latent frames: two frame batches (conv caches in front of every causal convolution, the odd-clip first-frame rules);
+    2 latent frames: the even-clip rules."""
+    ref, m = make(REAL_WIDTHS, seed=13)
+    z = torch.randn(1, 16, frames, 4, 6, generator=torch.Generator().manual_seed(frames)).to(BF).float()
+    with torch.no_grad():
+        want = ref.decode(z)
+    got = m.decode(z.to("cuda:0", BF)).sample
+    assert got.shape == want.shape == (1, 3, 9 if frames == 3 else 8, 32, 48)
+    assert rel_l2(got, want) <= 3e-2
+
+
+def test_encode_matches_oracle_at_the_real_widths():
+    ref, m = make(REAL_WIDTHS, seed=14)
+    x = (torch.rand(1, 3, 9, 32, 48, generator=torch.Generator().manual_seed(9)) * 2 - 1).to(BF).float()
+    with torch.no_grad():
+        want = ref.encode(x)
+    dist = m.encode(x.to("cuda:0", BF)).latent_dist
+    assert dist.parameters.shape == want.parameters.shape == (1, 32, 3, 4, 6)
+    assert rel_l2(dist.parameters, want.parameters) <= 3e-2
+
+
+def test_patch_matrix_slabs_are_bit_identical_to_one_slab(monkeypatch):
+    """``_conv`` builds the patch matrix in slabs of at most ``_PATCH_BYTES``; at the default 2 GiB no test ever takes the loop twice.
+    With 2048-row slabs the 32-channel stage (M = 12288) runs six: same rows, same GEMM, the same bits."""
+    from orv_amd import ops, vae as V
+    _, m = make(TINY, seed=15)
+    z = torch.randn(1, 16, 2, 4, 6, generator=torch.Generator().manual_seed(2)).to("cuda:0", BF)
+    base = m.decode(z).sample
+    slabs = {}
+    real = ops.vae_im2col
+
+    def counting(src, dst, B, Ts, Hs, Ws, C, *rest):
+        slabs.setdefault((C, id(src)), []).append(rest[-2])            # m0 of every slab of one convolution input
+        return real(src, dst, B, Ts, Hs, Ws, C, *rest)
+
+    monkeypatch.setattr(ops, "vae_im2col", counting)
+    monkeypatch.setattr(V, "_PATCH_BYTES", 2 * 896 * 2048)
+    got = m.decode(z).sample
+    assert max(len(set(v)) for (c, _), v in slabs.items() if c == 32) >= 3
+    assert torch.equal(got, base)
+
+
+def test_decode_without_the_implicit_gemm_meets_the_oracle_bound(monkeypatch):
+    """ORV_VAE_IMPLICIT_GEMM=0's path (patch matrix + plain GEMM for every convolution) is a second implementation of the same function."""
+    from orv_amd import vae as V
+    ref, m = make(TINY, seed=16)
+    z = torch.randn(2, 16, 3, 4, 6, generator=torch.Generator().manual_seed(3)).to(BF).float()
+    with torch.no_grad():
+        want = ref.decode(z)
+    monkeypatch.setattr(V, "_IMPLICIT_GEMM", False)
+    assert rel_l2(m.decode(z.to("cuda:0", BF)).sample, want) <= 3e-2
+
+
 def test_decode_frame_batching_rules():
     """diffusers decodes in batches of 2 latent frames (first batch takes the remainder: 5 = 3 + 2) with every causal
     convolution's conv_cache carried over and GroupNorm computed per batch.  So: a change confined to the second batch's latent
