@@ -517,6 +517,43 @@ int orv_gs_render(const int* ranges, const int* point_list, long L, const float*
                   const float* depth, const float* colors, const float* features, int N, int F, const float* bg, int H, int W,
                   float* out_color, float* out_feature, float* out_depth, float* out_alpha, void* stream);
 
+/* -- Point-cloud voxelization: ORV's occupancy preparation --------------------------------------------------------------------------
+ * Hard, dynamic and semantic voxelization of a point cloud points [N, C] (fp32, x y z first), replacing the CUDA extension orv/ops/voxelize
+ * (Python surface orv/ops/voxelize/voxelization.py:42-122) that points_to_voxels (orv/dataset/prepare_dataset.py:137-198) calls for every
+ * frame from get_occupancy (:887-1039).  The definition is the sequential walk of orv/ops/voxelize/voxelization_cpu.cpp:71-102; the
+ * arithmetic contract - fp32 (p - lo) / vs with a correctly rounded divide, grid = round((hi - lo) / vs) in fp32, voxels in order of first
+ * appearance, slots in point order, the two caps, the vote's tie rule - is written out in DESIGN.md section 13.  Integer and copied-float
+ * outputs, no order-dependent atomic: bit-reproducible.  voxel size (vx, vy, vz) and range (x0, y0, z0 = min; x1, y1, z1 = max) are passed
+ * by value, already rounded to fp32.  A voxelization is three or four calls with two torch steps between them:
+ *   coors -> stable sort of the keys -> segments (first zeroed) -> inclusive int32 cumsum(first), M = min(last, max_voxels) -> scatter | vote.
+ *
+ * Cells per axis (x, y, z) by the reference's rule (voxelization_cpu.cpp:118-121, :147-150).  Host only. */
+int orv_voxel_grid_size(float vx, float vy, float vz, float x0, float y0, float z0, float x1, float y1, float z1, int* grid);
+/* Per point (replaces dynamic_voxelize_kernel, orv/ops/include/voxelization_kernel.cuh:9-46, in the CPU form of voxelization_cpu.cpp:7-46):
+ * coors [N,3] int32 = (z, y, x) cell, or (-1, -1, -1) for a point outside the range or with a NaN / infinite coordinate; keys [N] int64 =
+ * (z * gy + y) * gx + x, the largest int64 for an invalid point (keys may be NULL: dynamic voxelization needs coors only).
+ * N = 0 launches nothing. */
+int orv_voxel_coors(const float* points, int N, int C, float vx, float vy, float vz, float x0, float y0, float z0, float x1, float y1,
+                    float z1, int* coors, long* keys, void* stream);
+/* On the stably sorted keys with order [N] int64 = the point of each sorted entry (replaces point_to_voxelidx_kernel,
+ * voxelization_kernel.cuh:91-132, where every point scans all earlier points): start [N] = sorted position of the entry's segment head
+ * (-1 for an invalid point), seglen [N] = the segment's length at its head (0 elsewhere), first [N] (zeroed by the caller) = 1 at the
+ * point that opens a voxel. */
+int orv_voxel_segments(const long* sorted_keys, const long* order, int N, int* start, int* seglen, int* first, void* stream);
+/* Hard voxelization's output (replaces determin_voxel_num <<<1, 1>>> and assign_point_to_voxel / assign_voxel_coors,
+ * voxelization_kernel.cuh:134-163 and :48-88): csum [N] int32 = inclusive prefix sum of first, M = min(csum[N-1], max_voxels).  An entry of
+ * voxel csum[first point] - 1 < M with rank < max_points copies its C features to voxels [M, max_points, C] (zeroed by the caller); the
+ * head writes coors [M,3] (z, y, x) and num_points_per_voxel [M] = min(length, max_points).  N = 0 or M = 0 launches nothing. */
+int orv_voxel_scatter(const float* points, const int* point_coors, const long* order, const int* start, const int* seglen,
+                      const int* csum, int N, int C, int max_points, int M, float* voxels, int* coors, int* num_points_per_voxel,
+                      void* stream);
+/* The semantic vote fused with the scatter (replaces the torch post-processing of prepare_dataset.py:179-196 on the voxels buffer, which
+ * is never built): the last feature holds label + 1 with 0 <= label < 255; out [M,4] int32 = (x, y, z, label), label = the most frequent
+ * stored label among the voxel's first min(length, max_points) points, minus one, a tie going to the smallest label.  One wave per voxel.
+ * head_of [M] int32 is scratch, filled with -1 by the caller.  N = 0 or M = 0 launches nothing. */
+int orv_voxel_vote(const float* points, const int* point_coors, const long* order, const int* start, const int* seglen, const int* csum,
+                   int N, int C, int max_points, int M, int* head_of, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

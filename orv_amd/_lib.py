@@ -141,6 +141,11 @@ SIGNATURES = {
     "orv_gs_tile_keys": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "orv_gs_tile_ranges": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
     "orv_gs_render": (c_int, [c_void_p, c_void_p, c_long] + [c_void_p] * 5 + [c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5),
+    "orv_voxel_grid_size": (c_int, [c_float] * 9 + [c_void_p]),
+    "orv_voxel_coors": (c_int, [c_void_p, c_int, c_int] + [c_float] * 9 + [c_void_p, c_void_p, c_void_p]),
+    "orv_voxel_segments": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "orv_voxel_scatter": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 4),
+    "orv_voxel_vote": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 3),
 }
 
 _lib = None

@@ -844,3 +844,72 @@ def gs_render(ranges, point_list, xy, conic_opacity, depth, colors, features, bg
                                   _p(features) if F else None, N, F, _p(bg), int(H), int(W), _p(color), _p(feat) if F else None, _p(dep),
                                   _p(alpha), _stream()), "orv_gs_render")
     return color, feat, dep, alpha
+
+
+# ---- point-cloud voxelization (voxelize.hip) ----
+def voxel_grid_size(voxel_size, coors_range):
+    """Cells per axis (x, y, z) of ``coors_range`` [6] cut into ``voxel_size`` [3] (fp32 values): round((hi - lo) / vs) in fp32.  Host only."""
+    import ctypes
+    grid = (ctypes.c_int * 3)()
+    check(lib().orv_voxel_grid_size(*[float(v) for v in voxel_size], *[float(v) for v in coors_range], ctypes.addressof(grid)),
+          "orv_voxel_grid_size")
+    return tuple(grid)
+
+
+def voxel_coors(points, voxel_size, coors_range, want_keys=True):
+    """-> (coors int32 [N,3] in (z, y, x) order, -1 rows for points outside the grid; keys int64 [N] or None)."""
+    _need_c(points, torch.float32, "points")
+    if points.dim() != 2:
+        raise ValueError(f"voxel_coors: points must be [N,C] (got {tuple(points.shape)})")
+    N, C = points.shape
+    coors = torch.empty(N, 3, dtype=torch.int32, device=points.device)
+    keys = torch.empty(N, dtype=torch.int64, device=points.device) if want_keys else None
+    check(lib().orv_voxel_coors(_p(points), N, C, *[float(v) for v in voxel_size], *[float(v) for v in coors_range], _p(coors), _p(keys),
+                                _stream()), "orv_voxel_coors")
+    return coors, keys
+
+
+def voxel_segments(sorted_keys, order):
+    """-> (start int32 [N], seglen int32 [N], first int32 [N]) of the stably sorted keys; ``order`` = the sort's int64 indices."""
+    _need_c(sorted_keys, torch.int64, "sorted_keys"), _need_c(order, torch.int64, "order")
+    _same_device((sorted_keys, "sorted_keys"), (order, "order"))
+    N = sorted_keys.numel()
+    if order.numel() != N:
+        raise ValueError("voxel_segments: sorted_keys [N], order [N]")
+    start, seglen = torch.empty(N, dtype=torch.int32, device=order.device), torch.empty(N, dtype=torch.int32, device=order.device)
+    first = torch.zeros(N, dtype=torch.int32, device=order.device)
+    check(lib().orv_voxel_segments(_p(sorted_keys), _p(order), N, _p(start), _p(seglen), _p(first), _stream()), "orv_voxel_segments")
+    return start, seglen, first
+
+
+def _voxel_inputs(points, point_coors, order, start, seglen, csum, who):
+    _need_c(points, torch.float32, "points"), _need_c(point_coors, torch.int32, "point_coors"), _need_c(order, torch.int64, "order")
+    _need_c(start, torch.int32, "start"), _need_c(seglen, torch.int32, "seglen"), _need_c(csum, torch.int32, "csum")
+    _same_device((points, "points"), (point_coors, "point_coors"), (order, "order"), (start, "start"), (seglen, "seglen"), (csum, "csum"))
+    N = points.shape[0]
+    if points.dim() != 2 or point_coors.numel() != 3 * N or any(t.numel() != N for t in (order, start, seglen, csum)):
+        raise ValueError(f"{who}: points [N,C], point_coors [N,3], order / start / seglen / csum [N]")
+    return N, points.shape[1]
+
+
+def voxel_scatter(points, point_coors, order, start, seglen, csum, max_points, M):
+    """-> (voxels [M, max_points, C] zero-padded, coors int32 [M,3], num_points_per_voxel int32 [M])."""
+    N, C = _voxel_inputs(points, point_coors, order, start, seglen, csum, "voxel_scatter")
+    dev = points.device
+    voxels = torch.zeros(M, max_points, C, dtype=torch.float32, device=dev)
+    coors, num = torch.zeros(M, 3, dtype=torch.int32, device=dev), torch.zeros(M, dtype=torch.int32, device=dev)
+    with _timed(("voxel_scatter", N, C, max_points, M)):
+        check(lib().orv_voxel_scatter(_p(points), _p(point_coors), _p(order), _p(start), _p(seglen), _p(csum), N, C, int(max_points), int(M),
+                                      _p(voxels), _p(coors), _p(num), _stream()), "orv_voxel_scatter")
+    return voxels, coors, num
+
+
+def voxel_vote(points, point_coors, order, start, seglen, csum, max_points, M):
+    """-> int32 [M,4] = (x, y, z, label) per kept voxel; the last feature of ``points`` holds label + 1."""
+    N, C = _voxel_inputs(points, point_coors, order, start, seglen, csum, "voxel_vote")
+    head_of = torch.full((M,), -1, dtype=torch.int32, device=points.device)
+    out = torch.empty(M, 4, dtype=torch.int32, device=points.device)
+    with _timed(("voxel_vote", N, C, max_points, M)):
+        check(lib().orv_voxel_vote(_p(points), _p(point_coors), _p(order), _p(start), _p(seglen), _p(csum), N, C, int(max_points), int(M),
+                                   _p(head_of), _p(out), _stream()), "orv_voxel_vote")
+    return out
