@@ -554,6 +554,43 @@ int orv_voxel_scatter(const float* points, const int* point_coors, const long* o
 int orv_voxel_vote(const float* points, const int* point_coors, const long* order, const int* start, const int* seglen, const int* csum,
                    int N, int C, int max_points, int M, int* head_of, int* out, void* stream);
 
+/* -- Occupancy labelling and sparse Gaussian scene preparation ------------------------------------------------------------------------
+ * The two steps of ORV's conditioning chain between the voxelization above and the rasterizer: labelling a frame's surface points from
+ * its 2-D label image (project_3d_to_2d, orv/dataset/prepare_dataset.py:878-884, and the labelling block of get_occupancy, :999-1008),
+ * and turning a frame's occupancy rows into the Gaussians get_render splats (prepare_dataset.py:2069-2086 and :2148-2164) without any
+ * buffer the size of the 400^3 grid.  The arithmetic contract is written out in DESIGN.md section 14.  The only atomics are integer ORs
+ * on a flag and a bitmap, so every output is bit-reproducible.  A scene preparation is three calls with two torch steps between them:
+ *   cell_keys -> stable sort of the keys -> mark_cells -> inclusive int32 cumsum(last), one host read of (bitmap, flag, count) ->
+ *   write_gaussians.
+ *
+ * Per point (replaces project_3d_to_2d, prepare_dataset.py:878-884, and the gather and relabelling of :999-1008): P is the device pointer
+ * of the row-major fp32 4 x 4 matrix intrin4 @ inverse(extrin) (rows 0 to 2 are read; it is never read on the host).  For j = 0, 1, 2
+ * h_j = ((x P[j][0] + y P[j][1]) + z P[j][2]) + P[j][3] with every product and sum rounded to fp32 on its own (no fused multiply-add),
+ * u = h_0 / h_2 and v = h_1 / h_2 by a correctly rounded divide, then truncated toward zero.  A point is inside when 0 <= trunc(u) < W
+ * and 0 <= trunc(v) < H: u in (-1, 0) counts as column 0, a point behind the camera counts when it lands inside, a NaN or infinite u or
+ * v is outside.  labels3d [N] int64 = labels2d[v][u] with 255 (and -1) -> 59 for a point inside, 0 outside.  labels2d [H, W] holds
+ * label_bytes = 1 (uint8) or 4 (int32) per pixel.  N = 0 launches nothing. */
+int orv_occ_project_labels(const float* points, int N, int C, const float* P, const void* labels2d, int label_bytes, int H, int W,
+                           long* labels3d, void* stream);
+/* Per occupancy row occ [M,4] int32 = (x, y, z, label) (replaces the two dense scatters of prepare_dataset.py:2153-2154 and :2162-2163
+ * into 64 M-cell grids): keys [M] int64 = the dense linear index (x Y + y) Z + z, the largest int64 for a row outside the X x Y x Z grid,
+ * which also sets state[1] (state [3] int64, zeroed by the caller: class bitmap, out-of-grid flag, spare).  M = 0 launches nothing. */
+int orv_occ_cell_keys(const int* occ, int M, int X, int Y, int Z, long* keys, long* state, void* stream);
+/* On the stably sorted keys with order [M] int64 = the row of each sorted entry (replaces torch.unique over the 64 M-cell grid,
+ * prepare_dataset.py:2155-2157): last [M] int32 = 1 at the entry that closes its cell's segment - the cell's last row, whose label the
+ * dense scatter keeps - else 0; the labels of those rows, clamped to [0, 59], are ORed into the bitmap state[0]. */
+int orv_occ_mark_cells(const long* sorted_keys, const long* order, const int* occ, int M, int* last, long* state, void* stream);
+/* Every attribute of the n surviving cells in ascending order of the dense index (replaces the [64 M, 12] one-hot of
+ * prepare_dataset.py:2158 and the six boolean gathers of :2175 over the dense tensors of :2077-2086): csum [M] int32 = inclusive prefix
+ * sum of last, n = csum[M-1]; order and occ as in mark_cells (the cell's coordinates are read from its row); classes = the bitmap, with bit 0 set by the caller when the grid has an empty cell.  Gaussian g gets
+ * xyz [n,3] = (ax[x], ay[y], az[z]) from the three axis tables, rgb [n,3] = 0, feat [n,F] = the one-hot of popcount(classes below the
+ * label), rot [n,4] = (1, 0, 0, 0), scale [n,3] = zscale[z] three times, opacity [n,1] = 1.  More classes than F channels is refused.
+ * M = 0 or n = 0 launches nothing. */
+int orv_occ_write_gaussians(const long* order, const int* occ, const int* last, const int* csum, int M, int n,
+                            int X, int Y, int Z, const float* ax, const float* ay, const float* az, const float* zscale,
+                            unsigned long classes, int F, float* xyz, float* rgb, float* feat, float* rot, float* scale, float* opacity,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_uint, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_uint, c_ulong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ORV_LIB: another build of the same library (developer A/B runs: tools/*.sh); the default is the in-tree build
@@ -146,6 +146,10 @@ SIGNATURES = {
     "orv_voxel_segments": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "orv_voxel_scatter": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 4),
     "orv_voxel_vote": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 3),
+    "orv_occ_project_labels": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "orv_occ_cell_keys": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 3),
+    "orv_occ_mark_cells": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3),
+    "orv_occ_write_gaussians": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4 + [c_ulong, c_int] + [c_void_p] * 7),
 }
 
 _lib = None

@@ -913,3 +913,75 @@ def voxel_vote(points, point_coors, order, start, seglen, csum, max_points, M):
         check(lib().orv_voxel_vote(_p(points), _p(point_coors), _p(order), _p(start), _p(seglen), _p(csum), N, C, int(max_points), int(M),
                                    _p(head_of), _p(out), _stream()), "orv_voxel_vote")
     return out
+
+
+# ---- occupancy labelling and sparse Gaussian scene preparation (occupancy.hip) ----
+def occ_project_labels(points, P, labels2d):
+    """points fp32 [N,C], P fp32 [4,4] (intrin4 @ inverse(extrin), on the device), labels2d uint8 or int32 [H,W] -> labels int64 [N]."""
+    _need_c(points, torch.float32, "points"), _need_c(P, torch.float32, "P")
+    if labels2d.dtype not in (torch.uint8, torch.int32):
+        raise RuntimeError(f"orv_amd.ops: `labels2d` must be torch.uint8 or torch.int32 (got {labels2d.dtype})")
+    _need_c(labels2d, labels2d.dtype, "labels2d")
+    _same_device((points, "points"), (P, "P"), (labels2d, "labels2d"))
+    if points.dim() != 2 or tuple(P.shape) != (4, 4) or labels2d.dim() != 2:
+        raise ValueError(f"occ_project_labels: points [N,C], P [4,4], labels2d [H,W] (got {tuple(points.shape)}, {tuple(P.shape)}, {tuple(labels2d.shape)})")
+    N, C = points.shape
+    H, W = labels2d.shape
+    out = torch.empty(N, dtype=torch.int64, device=points.device)
+    with _timed(("occ_project_labels", N, C, H, W)):
+        check(lib().orv_occ_project_labels(_p(points), N, C, _p(P), _p(labels2d), labels2d.element_size(), H, W, _p(out), _stream()),
+              "orv_occ_project_labels")
+    return out
+
+
+def occ_cell_keys(occ, grid, state):
+    """occ int32 [M,4] = (x, y, z, label), grid = (X, Y, Z), state int64 [3] zeroed -> keys int64 [M]; state[1] is set by a row outside the grid."""
+    _need_c(occ, torch.int32, "occ"), _need_c(state, torch.int64, "state")
+    _same_device((occ, "occ"), (state, "state"))
+    if occ.dim() != 2 or occ.shape[1] != 4 or state.numel() != 3:
+        raise ValueError(f"occ_cell_keys: occ [M,4], state [3] (got {tuple(occ.shape)}, {tuple(state.shape)})")
+    M = occ.shape[0]
+    keys = torch.empty(M, dtype=torch.int64, device=occ.device)
+    with _timed(("occ_cell_keys", M)):
+        check(lib().orv_occ_cell_keys(_p(occ), M, int(grid[0]), int(grid[1]), int(grid[2]), _p(keys), _p(state), _stream()), "orv_occ_cell_keys")
+    return keys
+
+
+def occ_mark_cells(sorted_keys, order, occ, state):
+    """-> last int32 [M]: 1 at the sorted entry that closes its cell; the clamped labels of those rows are ORed into state[0]."""
+    _need_c(sorted_keys, torch.int64, "sorted_keys"), _need_c(order, torch.int64, "order"), _need_c(occ, torch.int32, "occ")
+    _need_c(state, torch.int64, "state")
+    _same_device((sorted_keys, "sorted_keys"), (order, "order"), (occ, "occ"), (state, "state"))
+    M = sorted_keys.numel()
+    if order.numel() != M or occ.numel() != 4 * M or state.numel() != 3:
+        raise ValueError("occ_mark_cells: sorted_keys [M], order [M], occ [M,4], state [3]")
+    last = torch.empty(M, dtype=torch.int32, device=occ.device)
+    with _timed(("occ_mark_cells", M)):
+        check(lib().orv_occ_mark_cells(_p(sorted_keys), _p(order), _p(occ), M, _p(last), _p(state), _stream()), "orv_occ_mark_cells")
+    return last
+
+
+def occ_write_gaussians(order, occ, last, csum, n, grid, axes, zscale, classes, num_channels):
+    """-> (xyz [n,3], rgb [n,3], feat [n,F], rot [n,4], scale [n,3], opacity [n,1]) of the n surviving cells, in ascending order of the dense
+    linear index; ``axes`` = the three fp32 coordinate tables, ``zscale`` the per-z scale table, ``classes`` the class bitmap."""
+    _need_c(order, torch.int64, "order"), _need_c(occ, torch.int32, "occ")
+    _need_c(last, torch.int32, "last"), _need_c(csum, torch.int32, "csum"), _need_c(zscale, torch.float32, "zscale")
+    named = [(order, "order"), (occ, "occ"), (last, "last"), (csum, "csum"), (zscale, "zscale")]
+    for t, name in zip(axes, ("axes[0]", "axes[1]", "axes[2]")):
+        named.append((_need_c(t, torch.float32, name), name))
+    _same_device(*named)
+    M, (X, Y, Z), F = order.numel(), [int(g) for g in grid], int(num_channels)
+    if occ.numel() != 4 * M or last.numel() != M or csum.numel() != M:
+        raise ValueError("occ_write_gaussians: order / last / csum [M], occ [M,4]")
+    if [t.numel() for t in axes] != [X, Y, Z] or zscale.numel() != Z:
+        raise ValueError(f"occ_write_gaussians: the tables must hold {X}, {Y}, {Z} coordinates and {Z} scales")
+    dev, f32 = occ.device, torch.float32
+    n = int(n)
+    xyz, rgb, scale = (torch.empty(max(n, 0), 3, dtype=f32, device=dev) for _ in range(3))
+    feat, rot = torch.empty(max(n, 0), max(F, 0), dtype=f32, device=dev), torch.empty(max(n, 0), 4, dtype=f32, device=dev)
+    opacity = torch.empty(max(n, 0), 1, dtype=f32, device=dev)
+    with _timed(("occ_write_gaussians", M, n, F)):
+        check(lib().orv_occ_write_gaussians(_p(order), _p(occ), _p(last), _p(csum), M, n, X, Y, Z, _p(axes[0]), _p(axes[1]),
+                                            _p(axes[2]), _p(zscale), int(classes), F, _p(xyz), _p(rgb), _p(feat), _p(rot), _p(scale),
+                                            _p(opacity), _stream()), "orv_occ_write_gaussians")
+    return xyz, rgb, feat, rot, scale, opacity
