@@ -591,6 +591,40 @@ int orv_occ_write_gaussians(const long* order, const int* occ, const int* last, 
                             unsigned long classes, int F, float* xyz, float* rgb, float* feat, float* rot, float* scale, float* opacity,
                             void* stream);
 
+/* -- Control encoding: rendered depth and label maps (or uint8 video frames) to the VAE encoder's input --------------------------------
+ * Replaces the per-frame torchvision loop of orv/dataset/dataset.py:225-295 and :852-888 and the repeat / permute of
+ * orv/dataset/encode_dataset.py:801-916, and writes what AutoencoderKLCogVideoX._channels_last(x, cpad=5) would.  The arithmetic contract
+ * (DESIGN.md section 15), all fp32:
+ *   plan     up to two stages of (resize to rh x rw, centre crop to ch x cw at (top, left)); stage 2 reads stage 1's cropped fp32 image.
+ *            A crop larger than its input and a downscale beyond 4 x per axis and stage are refused.
+ *   bilinear antialiased, per axis, n inputs -> o outputs: scale = float(n) / float(o); support = scale if scale >= 1 else 1; inv = 1 / scale
+ *            if scale >= 1 else 1; c = scale * (i + 0.5); lo = max(int(c - support + 0.5), 0), hi = min(int(c + support + 0.5), n); tap j
+ *            in [lo, hi) weighs max(0, 1 - |(j - c + 0.5) * inv|); the weights are summed in tap order and each is divided by the sum
+ *            (correctly rounded); the output is the sum in tap order of x[j] * w[j].  Every product and sum is rounded to fp32 on its own
+ *            (no FMA).  The horizontal pass comes first and is rounded to fp32, the vertical pass follows.
+ *   nearest  source index min(int(floorf(i * (float(n) / float(o)))), n - 1); two stages compose their index maps; ids are painted after.
+ *   post     depth: min(max(x, 0.01), 0.4) * 2.5; ids: palette[id] / 255; RGB: x / 255 before the resize, (x - 0.5) / 0.5 after the crop
+ *            with ORV_COND_POST_NORMALIZE.
+ * src [N, h, w] (fp32 or uint8 ids) or [N, h, w, 3] (uint8 RGB); palette fp32 [n_palette, 3] on the device (ids only; an id is validated by
+ * the caller, the kernel reads no entry past the table); index int32 [n_out] on the device = the source frame of every output frame
+ * (NULL: the identity; validated by the caller, an entry outside [0, N) gives a zero frame); plan = 6 host ints per stage (rh, rw, top,
+ * left, ch, cw).  out: ORV_COND_OUT_NCHW fp32 [n_out, C, H, W] (C = 1 for an fp32 source, else 3) or ORV_COND_OUT_VAE bf16
+ * [n_out, H, W, 8] (channels 0-2 the data, a single channel repeated three times, channels 3-7 zero; one 16-byte store per pixel), 16-byte
+ * aligned.  One launch, a workgroup per 16 x 16 tile of the final image; a two-stage bilinear plan keeps the stage-1 pixels its tile
+ * reaches in LDS.  No atomics: bit-reproducible.  n_out = 0 launches nothing. */
+#define ORV_COND_SRC_F32 0
+#define ORV_COND_SRC_IDS 1
+#define ORV_COND_SRC_RGB8 2
+#define ORV_COND_NEAREST 0
+#define ORV_COND_BILINEAR 1
+#define ORV_COND_POST_NONE 0
+#define ORV_COND_POST_DEPTH 1
+#define ORV_COND_POST_NORMALIZE 2
+#define ORV_COND_OUT_NCHW 0
+#define ORV_COND_OUT_VAE 1
+int orv_cond_prepare(const void* src, int src_kind, int N, int h, int w, const float* palette, int n_palette, const int* index, int n_out,
+                     const int* plan, int n_stage, int interp, int post, void* out, int out_kind, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,8 @@ SIGNATURES = {
     "orv_occ_cell_keys": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 3),
     "orv_occ_mark_cells": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3),
     "orv_occ_write_gaussians": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4 + [c_ulong, c_int] + [c_void_p] * 7),
+    "orv_cond_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, POINTER(c_int), c_int, c_int, c_int,
+                                 c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

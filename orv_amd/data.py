@@ -10,7 +10,8 @@ Mirrors (behaviour, not code) /root/reference/orv/dataset/dataset.py:
                                          latents_depth, latents_label}, num_views, num_frames, image_width/height}``
                                          with the ``[B, F, C, h, w] -> [B, C, F, h, w]`` permute the loop expects (:864-898)
 
-Raw-video / PIL branches (decord, torchvision transforms) belong to data preparation and are out of scope.
+Raw-video / PIL branches (decord) belong to data preparation and are out of scope; the transform chains and the encode step that
+turn render arrays or decoded uint8 frames into these moments are ``orv_amd.conditions``.
 """
 from __future__ import annotations
 

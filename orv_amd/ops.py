@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import ctypes
 import os
 import torch
 
@@ -985,3 +986,63 @@ def occ_write_gaussians(order, occ, last, csum, n, grid, axes, zscale, classes, 
                                             _p(axes[2]), _p(zscale), int(classes), F, _p(xyz), _p(rgb), _p(feat), _p(rot), _p(scale),
                                             _p(opacity), _stream()), "orv_occ_write_gaussians")
     return xyz, rgb, feat, rot, scale, opacity
+
+
+# ---- control encoding: render arrays / uint8 frames -> the VAE encoder's input (conditions.hip) ----
+COND_INTERP = {"nearest": 0, "bilinear": 1}
+COND_POST = {None: 0, "none": 0, "depth": 1, "normalize": 2}
+COND_OUT = {"nchw": 0, "vae": 1}
+
+
+def cond_prepare(src, stages, interp, post=None, index=None, palette=None, out="nchw"):
+    """src fp32 [N,h,w] (depth), uint8 [N,h,w] (label ids, with ``palette`` fp32 [P,3]) or uint8 [N,h,w,3] (RGB frames); ``stages`` = one or
+    two (rh, rw, top, left, ch, cw); ``index`` int32 [n_out] = the source frame of every output frame (None: all, in order;
+    an entry outside [0, N) gives a zero frame, ``orv_amd.conditions`` refuses it first) -> fp32 [n_out, C, H, W] (``out="nchw"``) or bf16 [n_out, H, W, 8] (``out="vae"``: channels 0-2 the data, 3-7 zero)."""
+    if not isinstance(src, torch.Tensor):
+        raise RuntimeError(f"orv_amd.ops: `src` must be a torch tensor on the GPU (got {type(src).__name__})")
+    if src.dtype == torch.float32 and src.dim() == 3:
+        kind = 0
+    elif src.dtype == torch.uint8 and src.dim() == 3:
+        kind = 1
+    elif src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3:
+        kind = 2
+    else:
+        raise RuntimeError("orv_amd.ops: `src` must be torch.float32 [N,h,w], torch.uint8 [N,h,w] (label ids) or torch.uint8 [N,h,w,3] (RGB) "
+                           f"(got {src.dtype} {tuple(src.shape)})")
+    named = [(src, "src")]
+    if (kind == 1) != (palette is not None):
+        raise ValueError("orv_amd.ops: `palette` goes with uint8 label ids [N,h,w] and with nothing else")
+    if palette is not None:
+        if palette.dim() != 2 or palette.shape[1] != 3:
+            raise ValueError(f"orv_amd.ops: `palette` must be [P,3] (got {tuple(palette.shape)})")
+        named.append((palette, "palette"))
+    if index is not None:
+        if index.dim() != 1:
+            raise ValueError(f"orv_amd.ops: `index` must be [n_out] (got {tuple(index.shape)})")
+        named.append((index, "index"))
+    for t, name in named:
+        if t.requires_grad:
+            raise RuntimeError(f"orv_amd.ops: `{name}` requires grad; cond_prepare has no backward (supported: tensors without grad)")
+        _need_c(t, {"src": src.dtype, "palette": torch.float32, "index": torch.int32}[name], name)
+    _same_device(*named)
+    if interp not in COND_INTERP or post not in COND_POST or out not in COND_OUT:
+        raise ValueError(f"orv_amd.ops: interp in {sorted(COND_INTERP)}, post in {[k for k in COND_POST if k]} or None, out in {sorted(COND_OUT)} "
+                         f"(got {interp!r}, {post!r}, {out!r})")
+    stages = [tuple(int(v) for v in s) for s in stages]
+    if len(stages) not in (1, 2) or any(len(s) != 6 for s in stages):
+        raise ValueError("orv_amd.ops: `stages` holds one or two (rh, rw, top, left, ch, cw)")
+    flat = [v for s in stages for v in s]
+    plan = (ctypes.c_int * len(flat))(*flat)
+    N, h, w = src.shape[:3]
+    n_out = N if index is None else index.numel()
+    H, W = stages[-1][4], stages[-1][5]
+    C = 1 if kind == 0 else 3
+    if out == "nchw":
+        res = torch.empty(n_out, C, max(H, 0), max(W, 0), dtype=torch.float32, device=src.device)
+    else:
+        res = torch.empty(n_out, max(H, 0), max(W, 0), 8, dtype=BF16, device=src.device)
+    with _timed(("cond_prepare", kind, n_out, h, w, H, W, COND_OUT[out])):
+        check(lib().orv_cond_prepare(_p(src), kind, N, h, w, _p(palette), 0 if palette is None else palette.shape[0], _p(index), n_out,
+                                     plan, len(stages), COND_INTERP[interp], COND_POST[post], _p(res), COND_OUT[out], _stream()),
+              "orv_cond_prepare")
+    return res

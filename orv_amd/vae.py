@@ -546,16 +546,24 @@ class AutoencoderKLCogVideoX(nn.Module):
         """x [B, 3, F, H, W] in [-1, 1] -> latent_dist over moments [B, 32, 1 + (F - 1) / 4, H / 8, W / 8]."""
         self._check(x)
         h = self._channels_last(x, cpad=(-x.shape[1]) % 8)            # RGB padded to 8 channels (zero weights beyond 3)
-        if self.use_tiling and (x.shape[-1] > self.tile_sample_min_width or x.shape[-2] > self.tile_sample_min_height):
+        dist = DiagonalGaussianDistribution(self.encode_channels_last(h, dtype=x.dtype))
+        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+
+    @torch.no_grad()
+    def encode_channels_last(self, h: torch.Tensor, dtype: torch.dtype = BF16):
+        """The part of ``encode`` behind ``_channels_last``: h bf16 [B, F, H, W, 8] (channels 0-2 the image, 3-7 zero), contiguous
+        -> moments [B, 32, 1 + (F - 1) / 4, H / 8, W / 8] in ``dtype``.  ``orv_amd.conditions`` writes ``h`` directly."""
+        self._check(h)
+        if h.dtype != BF16 or h.dim() != 5 or h.shape[-1] != 8 or not h.is_contiguous():
+            raise RuntimeError(f"orv_amd.vae.encode_channels_last takes a contiguous bf16 [B, F, H, W, 8] tensor (got {h.dtype} {tuple(h.shape)})")
+        if self.use_tiling and (h.shape[3] > self.tile_sample_min_width or h.shape[2] > self.tile_sample_min_height):
             bh = int(self.tile_latent_min_height * self.tile_overlap_factor_height)
             bw = int(self.tile_latent_min_width * self.tile_overlap_factor_width)
             h = self._tiled(self._encode_batch, h, self.num_sample_frames_batch_size, self.tile_sample_min_height,
                             self.tile_sample_min_width, bh, bw, self.tile_latent_min_height - bh, self.tile_latent_min_width - bw)
         else:
             h = self._batched(self._encode_batch, h, self.num_sample_frames_batch_size)
-        moments = h.permute(0, 4, 1, 2, 3).contiguous().to(x.dtype)
-        dist = DiagonalGaussianDistribution(moments)
-        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+        return h.permute(0, 4, 1, 2, 3).contiguous().to(dtype)
 
     def _padded_conv_in(self):
         """encoder.conv_in sees 3 input channels; the gather works on 16-byte channel groups, so a view of the convolution with
