@@ -25,6 +25,7 @@
 //     ascending, k halves 0, 1, the same k chunk per lane group), so the results are bit-identical to gemm_t8_kernel's.
 // Requires a_packed, K % 192 == 0 (three register sets, statically indexed: the K loop is unrolled by three), N % BN == 0, W < 4 GiB.
 #include "gemm_common.hpp"
+#include <type_traits>
 
 namespace {
 using namespace orv_gemm;
@@ -56,15 +57,15 @@ __device__ __forceinline__ unsigned long long d8_uniform64(unsigned long long u)
 // (as t8): lane (r16 = lane & 15, g = lane >> 4) holds, of block 2 P + t of a 64-column group, columns 32 P + 8 g + 4 t + (0..3) of row r16.
 // Every (16 rows x 64 columns) piece goes through the wave's 4-KiB fp32 scratch and comes back as lane = (row lane >> 3, 8-column chunk
 // lane & 7): loads and stores are 8 rows x one full 128-byte line per instruction.
-// residual register sets of the row-operand epilogues: 1 = the rows of a 64-column group are requested when the group starts (no spills); 2 = one
-// group ahead (10-34 VGPR spills at 256 registers).  Same box, interleaved x 3: FFN2 0.2953 -> 0.2937 ms, out-projection 0.0990 -> 0.0970 (profiles/r5_gemm_d8_b1.txt)
-#ifndef D8_RSETS
-#define D8_RSETS 1
-#endif
-// RLDS (row-operand epilogues at BN <= 192, where 32 KiB of LDS are free): the residual rows of a 64-column group arrive by LDS-DMA in a
-// per-wave 4-KiB slab ([32 rows][128 B], full-line pieces) instead of by register loads whose latency the epilogue would wait for - group
-// 0's is issued three K-tiles before the K loop ends (d8_issue_rows from the kernel), group g + 1's as soon as group g's rows have been
-// read out of the slab.  No registers are held across the wait.
+// Row-operand epilogues (2 = gated residual, 3 = GELU adjoint).  Up to round 6 the rows of a 64-column group were requested when the group
+// started, the bias behind them and the gate values inside the row-block loop, each used at once: every one of those loads sat BEHIND the
+// previous stores, and since the vector-memory counter retires in order, waiting for it meant waiting for those stores' acknowledgements too -
+// 41 full drains in gemm_d8_kernel<192, 2> against 10 in the plain kernel.  A second residual register set (D8_RSETS = 2, round 5) and the
+// slab below only moved the residual rows and left that chain in place, which is why both measured level.  Now d8_epilogue gathers bias and
+// gate before the tile's first store and rolls ONE residual set a group ahead (profiles/r7_gemm_gated_epilogue.txt).
+// RLDS (opt-in experiment, BN <= 192 where 32 KiB of LDS are free): the residual rows of a 64-column group arrive by LDS-DMA in a per-wave
+// 4-KiB slab ([32 rows][128 B], full-line pieces) - group 0's is issued three K-tiles before the K loop ends (d8_issue_rows from the kernel),
+// group g + 1's as soon as group g's rows have been read out of the slab.  It still drains once per group.
 __device__ __forceinline__ void d8_glds_v(const void* gsrc, const char* lds_dst) {
     const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)lds_dst);
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(gsrc), "s"(d) : "memory", "m0");
@@ -82,7 +83,7 @@ __device__ __forceinline__ void d8_issue_rows(const GemmArgs& p, const int row0,
 template <int BN, int EPI>
 constexpr bool d8_rlds() {
 #ifdef ORV_D8_RLDS       // opt-in build: measured level with the register loads (profiles/r5_gemm_d8_rlds.txt: FFN2 0.2907 vs 0.2903 ms, out-projection
-    return BN <= 192 && (EPI == 2 || EPI == 3);     // 0.0953 vs 0.0945) - the epilogue does not wait for its residual rows
+    return BN <= 192 && (EPI == 2 || EPI == 3);     // 0.0953 vs 0.0945) - it moved the residual rows only, the bias and gate loads kept the chain
 #else
     return false;
 #endif
@@ -103,7 +104,10 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
     }
     const int roff0 = rr8 * 256 + (((2 * c) ^ rr8) << 4), roff1 = rr8 * 256 + (((2 * c + 1) ^ rr8) << 4);      // + j * 2048
 
-    long orow[RB][2];
+    constexpr bool GATH = EPI == 2 || EPI == 3;
+    // output row numbers: 32 bits in the row-operand epilogues at BN = 256, which have no register to spare (launch_d8 checks the range)
+    using row_t = std::conditional_t<GATH && BN == 256, int, long>;
+    row_t orow[RB][2];
     bool valid[RB][2];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
@@ -113,43 +117,56 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
             valid[rb][j] = m < p.M;
             const int mc = min(m, p.M - 1);
             orow[rb][j] = mc;
-            if (p.c_rows > 0) orow[rb][j] = (long)(mc / p.c_rows) * p.c_bstride + p.c_off + mc % p.c_rows;
+            if (p.c_rows > 0) orow[rb][j] = (row_t)((long)(mc / p.c_rows) * p.c_bstride + p.c_off + mc % p.c_rows);
         }
-    // gate rows (EPI 2) of the two 16-row blocks: wave-uniform when a block lies inside one (batch element, token group) - the index
-    // arithmetic (integer divisions on the scalar unit) runs once per tile, not once per 64-column group
-    const float* gate_row[2] = {nullptr, nullptr};
-    bool gate_lane[2] = {false, false};
-    if (EPI == 2 && p.gate) {
+    // gate rows (EPI 2) of the wave's rows, found once per tile (integer divisions on the scalar unit).  Token groups are 226 / 600 rows long,
+    // so the 16 RB rows of a wave lie inside one (batch element, token group) or cross one boundary: gseg = 1: every row takes the gate row
+    // of the wave's first row (A); 2: A or the gate row of the wave's last row (B), in_a[rb][j] says which for this lane's row; 3: more
+    // than two gate rows (groups shorter than the wave's rows) - only then are the gate values loaded per lane in the loop.
+    const float *gate_a = nullptr, *gate_b = nullptr;
+    int gseg = 0;
+    bool in_a[RB][2];
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            const int mf = __builtin_amdgcn_readfirstlane(row0 + rb * 16), ml = min(mf + 15, p.M - 1);
-            long of = min(mf, p.M - 1), ol = ml;
-            if (p.c_rows > 0) {
-                of = (long)(of / p.c_rows) * p.c_bstride + p.c_off + of % p.c_rows;
-                ol = (long)(ml / p.c_rows) * p.c_bstride + p.c_off + ml % p.c_rows;
-            }
-            const int bf_ = (int)(of / p.seq), bl_ = (int)(ol / p.seq);
-            const int gf_ = orv_group_of((int)(of % p.seq), p.n_text, p.per_group);
-            const int gl_ = orv_group_of((int)(ol % p.seq), p.n_text, p.per_group);
-            if (bf_ == bl_ && gf_ == gl_) gate_row[rb] = p.gate + bf_ * p.gate_b + gf_ * p.gate_g;
-            else gate_lane[rb] = true;
+    for (int rb = 0; rb < RB; ++rb) in_a[rb][0] = in_a[rb][1] = true;
+    if (EPI == 2 && p.gate) {
+        const int mf = __builtin_amdgcn_readfirstlane(row0);
+        long of = min(mf, p.M - 1), ol = min(mf + 16 * RB - 1, p.M - 1);
+        if (p.c_rows > 0) {
+            of = (long)(of / p.c_rows) * p.c_bstride + p.c_off + of % p.c_rows;
+            ol = (long)(ol / p.c_rows) * p.c_bstride + p.c_off + ol % p.c_rows;
+        }
+        const int bf_ = (int)(of / p.seq), bl_ = (int)(ol / p.seq);
+        const int gf_ = orv_group_of((int)(of % p.seq), p.n_text, p.per_group);
+        const int gl_ = orv_group_of((int)(ol % p.seq), p.n_text, p.per_group);
+        gate_a = p.gate + bf_ * p.gate_b + gf_ * p.gate_g;
+        gseg = 1;
+        if (bf_ != bl_ || gf_ != gl_) {
+            gate_b = p.gate + bl_ * p.gate_b + gl_ * p.gate_g;
+            // rows ascend from the first to the last row of the wave (the uniform test above relies on the same): a row is in A below the end
+            // of A's (batch element, token group), in B from the start of B's - no division per lane
+            const int ea_ = gf_ == 0 ? p.n_text : (p.per_group > 0 ? p.n_text + gf_ * p.per_group : p.seq);
+            const long end_a = (long)bf_ * p.seq + min(ea_, p.seq);
+            const long start_b = (long)bl_ * p.seq + (gl_ == 0 ? 0 : p.n_text + (gl_ - 1) * max(p.per_group, 0));
+            bool other = false;
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    in_a[rb][j] = orow[rb][j] < end_a;
+                    other = other || !(in_a[rb][j] || orow[rb][j] >= start_b);
+                }
+            gseg = (BN == 256 || __builtin_amdgcn_ballot_w64(other) != 0) ? 3 : 2;       // BN = 256 has no registers for row B: per lane as well
         }
     }
-    // row operands (residual / GELU-adjoint input) of one 64-column group: requested one group ahead
-    constexpr int RS = (D8_RSETS == 0) ? (BN <= 192 ? NG : 1) : D8_RSETS;    // D8_RSETS = 0: every group's rows up front where the registers allow (BN <= 192)
-    uint4 r8[RS][RB][2];                                // [set][rb][j]
-    auto load_rows = [&](int cg, uint4 (&dst)[RB][2]) {
-        const int col8 = col0 + 64 * cg + 8 * c;
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int mc = min(row0 + rb * 16 + 8 * j + rr8, p.M - 1);
-                long rr = mc;
-                if (p.r_mod > 0) rr = mc % p.r_mod;
-                else if (p.c_rows > 0) rr = (long)(mc / p.c_rows) * p.c_bstride + p.c_off + mc % p.c_rows;
-                dst[rb][j] = *(const uint4*)(p.R + rr * p.ldr + col8);
-            }
+    // row operands (residual / GELU-adjoint input): ONE register set, rolling.  Group 0's rows are requested up front; the piece (rb, j) of
+    // group cg + 1 is requested into the registers of piece (rb, j) of group cg as soon as that one has been read, i.e. IN FRONT of the
+    // piece's own store and a whole group before it is used.  These loads are unconditional, so every wait of the loop is a counted one: it
+    // leaves the youngest stores in flight (d8_epilogue's note on the gather below; profiles/r7_gemm_gated_epilogue.txt).
+    uint4 r8[RB][2];                                    // [rb][j]
+    auto load_row = [&](int cg, int rb, int j) {
+        long rr = orow[rb][j];                          // the output row (row map included) unless the residual is a table
+        if (p.r_mod > 0) rr = min(row0 + rb * 16 + 8 * j + rr8, p.M - 1) % p.r_mod;
+        return *(const uint4*)(p.R + rr * p.ldr + col0 + 64 * cg + 8 * c);
     };
     // RLDS: rows of group cg out of the slab (the DMA was issued by the kernel / by the previous group), then the next group's DMA
     auto take_rows = [&](int cg, uint4 (&dst)[RB][2]) {
@@ -166,25 +183,63 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
         }
     };
     if (RLDS) {
-        take_rows(0, r8[0]);
-    } else if (EPI == 2 || EPI == 3) {
-        load_rows(0, r8[0]);
-        if (RS == NG && NG > 1 && !RLDS) {
+        take_rows(0, r8);
+    } else if (GATH) {
 #pragma unroll
-            for (int cg = 1; cg < NG; ++cg) load_rows(cg, r8[cg % RS]);
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) r8[rb][j] = load_row(0, rb, j);
+    }
+    // Gather (row-operand epilogues): every bias and gate value of the tile is requested HERE, before the tile's first store, in "source
+    // layout" - lane l holds column 64 cg + l, ONE register per (64-column group, row) - and handed to the lanes that need it (lane (row
+    // lane >> 3, chunk c) wants columns 8 c .. 8 c + 7) by ds_bpermute in the loop.  The vector-memory counter retires in order: a load issued
+    // behind a store can only be waited for together with that store's acknowledgement, and the old form (bias per group, gate values per row
+    // block, each used at once) was a chain of ~30 such round trips per tile and wave.
+    const int bp = c << 5;                              // ds_bpermute byte address of lane 8 c
+    uint32_t bsrc[NG];
+    float gsrc_a[NG], gsrc_b[NG];                       // gate rows A and B
+#pragma unroll
+    for (int cg = 0; cg < NG; ++cg) { bsrc[cg] = 0; gsrc_a[cg] = gsrc_b[cg] = 1.f; }
+    if constexpr (GATH) {
+        if (p.bias) {
+#pragma unroll
+            for (int cg = 0; cg < NG; ++cg) bsrc[cg] = p.bias[col0 + 64 * cg + lane];
+        }
+        if (gseg == 1 || gseg == 2) {
+#pragma unroll
+            for (int cg = 0; cg < NG; ++cg) gsrc_a[cg] = gate_a[col0 + 64 * cg + lane];
+        }
+        if (gseg == 2) {
+#pragma unroll
+            for (int cg = 0; cg < NG; ++cg) gsrc_b[cg] = gate_b[col0 + 64 * cg + lane];
         }
     }
+    // out[e] = src of lane 8 c + e.  Inline asm for the instruction's offset field: the builtin keeps eight address registers alive instead.
+    auto spread8 = [&](uint32_t src, uint32_t (&o)[8]) {
+        asm volatile("ds_bpermute_b32 %0, %8, %9\n\tds_bpermute_b32 %1, %8, %9 offset:4\n\tds_bpermute_b32 %2, %8, %9 offset:8\n\t"
+                     "ds_bpermute_b32 %3, %8, %9 offset:12\n\tds_bpermute_b32 %4, %8, %9 offset:16\n\tds_bpermute_b32 %5, %8, %9 offset:20\n\t"
+                     "ds_bpermute_b32 %6, %8, %9 offset:24\n\tds_bpermute_b32 %7, %8, %9 offset:28\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
+                     : "v"(bp), "v"(src));
+    };
 
 #pragma unroll
     for (int cg = 0; cg < NG; ++cg) {
         const int col8 = col0 + 64 * cg + 8 * c;
-        if (!RLDS && RS == 2 && RS != NG && (EPI == 2 || EPI == 3) && cg + 1 < NG) load_rows(cg + 1, r8[(cg + 1) & 1]);
-        if (RLDS) { if (cg > 0) take_rows(cg, r8[0]); }
-        else if (RS == 1 && (EPI == 2 || EPI == 3) && cg > 0) load_rows(cg, r8[0]);
+        if (RLDS && cg > 0) take_rows(cg, r8);
         float b8[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) b8[e] = 0.f;
-        if (p.bias) d8_unpack8(*(const uint4*)(p.bias + col8), b8);
+        if (p.bias) {
+            if constexpr (GATH) {
+                uint32_t o[8];
+                spread8(bsrc[cg], o);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) b8[e] = bf2f((bf16_t)o[e]);
+            } else {
+                d8_unpack8(*(const uint4*)(p.bias + col8), b8);
+            }
+        }
         // epilogue 4: qk LayerNorm parameters of this lane's 8 channels of the head (the 64-column group IS one head)
         float ga[8], be[8];
         int region = 2;
@@ -199,35 +254,39 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
             if (region < 2 && gam) d8_unpack8(*(const uint4*)(gam + 8 * c), ga);
             if (region < 2 && bet) d8_unpack8(*(const uint4*)(bet + 8 * c), be);
         }
-        float g8[8];
-        const float* g_cached = nullptr;
+        float g8[8];                                     // gate row A, this lane's 8 columns of the group
 #pragma unroll
         for (int e = 0; e < 8; ++e) g8[e] = 1.f;
+        if (gseg == 1 || gseg == 2) {
+            uint32_t o[8];
+            spread8(__float_as_uint(gsrc_a[cg]), o);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g8[e] = __uint_as_float(o[e]);
+        }
 
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
             for (int blk = 0; blk < 4; ++blk) *(f32x4*)(scr + woff[blk]) = acc[rb][4 * cg + blk];
             float v[2][8];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
+            auto read_v = [&](int j) {
                 const f32x4 lo = *(const f32x4*)(scr + j * 2048 + roff0), hi = *(const f32x4*)(scr + j * 2048 + roff1);
                 v[j][0] = lo[0]; v[j][1] = lo[1]; v[j][2] = lo[2]; v[j][3] = lo[3];
                 v[j][4] = hi[0]; v[j][5] = hi[1]; v[j][6] = hi[2]; v[j][7] = hi[3];
-            }
-            // gate row of this 16-row block (EPI 2): found once per tile (gate_row[] above), the values of this group's columns loaded here
-            const bool g_lane = (EPI == 2 && p.gate) ? gate_lane[rb] : false;
-            if (EPI == 2 && p.gate && !g_lane) {
-                const float* gr = gate_row[rb];
-                if (gr != g_cached) {
-                    g_cached = gr;
-                    const float4 a = *(const float4*)(gr + col8), b = *(const float4*)(gr + col8 + 4);
-                    g8[0] = a.x; g8[1] = a.y; g8[2] = a.z; g8[3] = a.w; g8[4] = b.x; g8[5] = b.y; g8[6] = b.z; g8[7] = b.w;
-                }
-            }
+            };
+            if constexpr (!GATH) { read_v(0); read_v(1); }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
+                if constexpr (GATH) {       // one row at a time (8 registers less at the point where everything else is alive)
+                    asm volatile("" ::: "memory");
+                    read_v(j);
+                }
                 float (&w)[8] = v[j];
+                uint4 rcur;
+                if constexpr (GATH) {
+                    rcur = r8[rb][j];
+                    if (!RLDS && cg + 1 < NG) r8[rb][j] = load_row(cg + 1, rb, j);
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) w[e] += b8[e];
                 bf16_t* crow = p.C + orow[rb][j] * p.ldc + col8;
@@ -268,21 +327,37 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
                 }
                 if (EPI == 2) {
                     float rv[8], gg[8];
-                    d8_unpack8(r8[RLDS ? 0 : cg % RS][rb][j], rv);
+                    d8_unpack8(rcur, rv);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) gg[e] = g8[e];
-                    if (g_lane) {            // block straddles a frame / text boundary: this lane's row picks its own gate row
-                        const int bidx = (int)(orow[rb][j] / p.seq), sq_ = (int)(orow[rb][j] % p.seq);
-                        const float* grow = p.gate + bidx * p.gate_b + orv_group_of(sq_, p.n_text, p.per_group) * p.gate_g;
-                        const float4 a = *(const float4*)(grow + col8), b = *(const float4*)(grow + col8 + 4);
-                        gg[0] = a.x; gg[1] = a.y; gg[2] = a.z; gg[3] = a.w; gg[4] = b.x; gg[5] = b.y; gg[6] = b.z; gg[7] = b.w;
+                    if (gseg == 2) {         // the wave crosses one group boundary: this lane's row takes gate row A or B
+                        uint32_t o[8];
+                        spread8(__float_as_uint(gsrc_b[cg]), o);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) gg[e] = in_a[rb][j] ? g8[e] : __uint_as_float(o[e]);
+                    }
+                    // more gate rows than the gather holds: this lane's rows pick their own.  Both rows of the block are loaded here (one wait
+                    // per block, on this path only); row 1's values wait in g8, which this path does not use otherwise
+                    if (gseg == 3 && j == 0) {
+                        f32x4 q[2][2];
+#pragma unroll
+                        for (int jj = 0; jj < 2; ++jj) {
+                            const unsigned o_ = (unsigned)orow[rb][jj];          // below 2^31: launch_d8 checks (a 32-bit division per lane)
+                            const int bidx = (int)(o_ / (unsigned)p.seq), sq_ = (int)(o_ - (unsigned)bidx * (unsigned)p.seq);
+                            const float* grow = p.gate + bidx * p.gate_b + orv_group_of(sq_, p.n_text, p.per_group) * p.gate_g;
+                            q[jj][0] = *(const f32x4*)(grow + col8);
+                            q[jj][1] = *(const f32x4*)(grow + col8 + 4);
+                        }
+                        asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]), "+v"(q[1][0]), "+v"(q[1][1]));
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) { gg[e] = q[0][e >> 2][e & 3]; g8[e] = q[1][e >> 2][e & 3]; }
                     }
 #pragma unroll
                     for (int e = 0; e < 8; ++e) w[e] = rv[e] + gg[e] * w[e];
                 }
                 if (EPI == 3) {
                     float rv[8];
-                    d8_unpack8(r8[RLDS ? 0 : cg % RS][rb][j], rv);
+                    d8_unpack8(rcur, rv);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) w[e] *= gelu_tanh_grad(rv[e]);
                 }
@@ -578,6 +653,15 @@ __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
 #else
         if ((EPI == 0 || EPI == 1) && p.c_packed) d8_epilogue_packed<BN, EPI, RB>(p, acc, tm * BM + wrb * 16, tn * BN, lane);
         else d8_epilogue<BN, EPI, RB>(p, acc, tm * BM + wrb * 16, tn * BN, lane, smem + SCR + wave * 4096, smem + SCR + 8 * 4096 + wave * 4096);
+        // BN = 256, row-operand epilogues: 128 accumulator registers + the A sets in flight + the next tile's first W fragments leave the
+        // epilogue too few registers - it spilled, and every spill reload is a load behind a store (a full drain).  The fragments are read
+        // AGAIN here instead of being kept across the epilogue (the buffer is complete since the last K-tile's barrier and is not refilled
+        // before the next tile's second K-tile): the same values, 16 registers free in the epilogue.
+        if constexpr (BN == 256 && (EPI == 2 || EPI == 3)) {
+            D8_FENCE()
+            _Pragma("unroll") for (int s_ = 0; s_ < 2 * CBP; ++s_) { D8_READ1(s_ % CBP, s_ / CBP, bufc * BUFSZ, 0) }
+            D8_FENCE()
+        }
 #endif
 #pragma unroll
         for (int a = 0; a < RB; ++a)
@@ -631,6 +715,15 @@ int launch_d8(const GemmArgs& a, int bn, int epi, hipStream_t st, int bm) {
     if (a.c_packed && (epi > 1 || a.ldc != a.N || a.c_rows > 0 || a.Y)) {
         orv_set_error("orv_gemm_bf16: packed C needs epilogue 0 / 1, ldc == N, no row map, no Y");
         return ORV_EINVAL;
+    }
+    if (epi == 2 || epi == 3) {
+        // the row-operand epilogues keep output row numbers (row map included) in 32 bits at BN = 256, and the gated one divides them per lane
+        // in 32 bits where a wave's rows touch more than two gate rows
+        const long last = a.c_rows > 0 ? (long)((a.M - 1) / a.c_rows) * a.c_bstride + a.c_off + a.c_rows - 1 : (long)a.M - 1;
+        if (last >= (1L << 31) || (epi == 2 && a.gate && a.seq <= 0)) {
+            orv_set_error("orv_gemm_bf16: the row-operand epilogues need output rows below 2^31 and seq > 0 (last row %ld, seq=%d)", last, a.seq);
+            return ORV_EINVAL;
+        }
     }
     if (bm == 192) {
         // 192-row tiles (gemm_d8r192_kernel): the packed A (and packed C) buffers hold orv_packed_rows(M) = ceil(M / 256) * 256 row slots and
