@@ -625,6 +625,46 @@ int orv_occ_write_gaussians(const long* order, const int* occ, const int* last, 
 int orv_cond_prepare(const void* src, int src_kind, int N, int h, int w, const float* palette, int n_palette, const int* index, int n_out,
                      const int* plan, int n_stage, int interp, int post, void* out, int out_kind, void* stream);
 
+/* -- Video metrics: per-frame PSNR and SSIM of a generated clip against its ground truth, on the device ---------------------------------
+ * Replaces the per-frame CPU loop of orv/pipeline/compute_metrics.py:38-80: cv2.resize(..., (320, 256), INTER_LINEAR) of both images,
+ * then skimage's peak_signal_noise_ratio and structural_similarity(channel_axis=-1, data_range=1.), spread over 64 threads.  The
+ * arithmetic contract.  PARITY UNPINNED: cv2 and skimage are not installed where this was written; the kernel is
+ * held to this contract, and the contract's SSIM to scipy.ndimage.uniform_filter in fp64 (the filter skimage calls).
+ *   source   fp32 is taken as it is; uint8 is (float)v / 255.0f (the reference's astype(float32) / 255.).
+ *   resize   per axis, n inputs -> o outputs (cv2's INTER_LINEAR for float images, restated from memory): scale = 1.0 / ((double)o /
+ *            (double)n); f = (float)(((double)i + 0.5) * scale - 0.5); s = floor(f); wt = f - (float)s; s < 0 gives s = 0, wt = 0;
+ *            s >= n - 1 gives s = n - 1, wt = 0; the second tap is min(s + 1, n - 1).  The horizontal pass comes first,
+ *            r = p[s] * (1.0f - wt) + p[s + 1] * wt, then the vertical pass over the two r rows in the same form; every product and sum is
+ *            rounded to fp32 on its own (no FMA).  o == n reproduces the source exactly: the supported way to skip the resize.
+ *   box mean 7 x 7: seven horizontal terms summed left to right in fp32, seven of those sums top to bottom, divided by 49.0f.
+ *   SSIM     skimage's defaults (win_size 7, uniform window, K1 = 0.01, K2 = 0.03, sample covariance), per channel, with the box means
+ *            ux, uy, uxx, uyy, uxy of a, b, a*a, b*b, a*b: cn = (float)(49.0 / 48.0); vx = cn * (uxx - ux * ux); vy likewise;
+ *            vxy = cn * (uxy - ux * uy); C1 = (float)((0.01 R)^2), C2 = (float)((0.03 R)^2) with R = data_range;
+ *            S = ((2 ux uy + C1) * (2 vxy + C2)) / ((ux ux + uy uy + C1) * (vx + vy + C2)), products and sums left to right as written,
+ *            the division correctly rounded.  S is averaged in fp64 over the pixels at distance >= 3 from every border (skimage's crop)
+ *            per channel; ssim = ((m0 + m1) + m2) / 3 of the three channel means.
+ *   PSNR     difference and square in fp32, sum in fp64; mse = sse / (3 h w); psnr = 10 log10(R^2 / mse) in fp64, inf when mse == 0.
+ * pred and gt each describe N frames of 3 channels by a device pointer, an element offset, element strides for (n, y, x, c), the number
+ * of elements of the buffer behind the pointer (every element the kernel can read is checked to lie inside it) and their own source
+ * height and width: uint8 or fp32 [N,H,W,3], fp32 [N,3,H,W] and width slices of either need no copy.  Both are resized to h x w (h, w
+ * >= 7).  out fp64 [3, N] = mse, psnr, ssim; ssim_map fp32 [N, h - 6, w - 6, 3] or NULL; workspace = orv_frame_metrics_workspace(N, h, w)
+ * bytes, 8-byte aligned, for one record of four fp64 sums per (frame, 32 x 32 tile).  Two launches: a workgroup per tile and frame keeps
+ * the resized block and its 3-pixel halo in LDS (the resized images never go to HBM), then one wave per frame sums the records in a fixed
+ * order.  No atomics on floating-point data: bit-reproducible.  N = 0 launches nothing. */
+#define ORV_METRICS_SRC_F32 0
+#define ORV_METRICS_SRC_U8 1
+typedef struct {
+    const void* data;      /* device pointer of the buffer */
+    int kind;              /* ORV_METRICS_SRC_* */
+    int h, w;              /* source height and width */
+    long extent;           /* elements in the buffer behind data */
+    long offset;           /* element offset of pixel (0, 0, 0, 0) */
+    long stride[4];        /* element strides of (n, y, x, c) */
+} orv_frames_t;
+long orv_frame_metrics_workspace(int N, int h, int w);
+int orv_frame_metrics(const orv_frames_t* pred, const orv_frames_t* gt, int N, int h, int w, double data_range, double* out,
+                      float* ssim_map, void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,4 +26,8 @@ def __getattr__(name):
     if name in ("FusedProdigy", "get_optimizer"):
         from . import optim
         return getattr(optim, name)
+    # the scoring stage of the reference's workflow (orv_amd/metrics.py), resolved on first use likewise
+    if name in ("frame_metrics", "psnr_ssim", "frechet_distance"):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

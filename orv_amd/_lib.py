@@ -35,6 +35,10 @@ class Conv(Structure):
                                                              "pad_lo", "ups_s", "ups_t", "t_shift")]
 
 
+class Frames(Structure):
+    _fields_ = [("data", c_void_p), ("kind", c_int), ("h", c_int), ("w", c_int), ("extent", c_long), ("offset", c_long), ("stride", c_long * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/orv_mi355.h declares
 SIGNATURES = {
     "orv_version": (c_int, []),
@@ -152,6 +156,8 @@ SIGNATURES = {
     "orv_occ_write_gaussians": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4 + [c_ulong, c_int] + [c_void_p] * 7),
     "orv_cond_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, POINTER(c_int), c_int, c_int, c_int,
                                  c_void_p, c_int, c_void_p]),
+    "orv_frame_metrics_workspace": (c_long, [c_int, c_int, c_int]),
+    "orv_frame_metrics": (c_int, [POINTER(Frames), POINTER(Frames), c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
 }
 
 _lib = None

@@ -1046,3 +1046,51 @@ def cond_prepare(src, stages, interp, post=None, index=None, palette=None, out="
                                      plan, len(stages), COND_INTERP[interp], COND_POST[post], _p(res), COND_OUT[out], _stream()),
               "orv_cond_prepare")
     return res
+
+
+# ---- video metrics (csrc/metrics.hip) ----
+METRICS_SUPPORTED = "supported: torch.uint8 or torch.float32 GPU tensors of N frames x 3 channels, without grad"
+
+
+def _frames_desc(t, name):
+    """A [N, H, W, 3] view of any strides -> the orv_frames_t the kernel gathers through (no copy)."""
+    from ._lib import Frames
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"orv_amd.ops: `{name}` must be a torch tensor on the GPU (got {type(t).__name__}); {METRICS_SUPPORTED}")
+    if not t.is_cuda:
+        raise RuntimeError(f"orv_amd.ops: `{name}` must live on the GPU (got {t.device}); there is no CPU path; {METRICS_SUPPORTED}")
+    if t.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f"orv_amd.ops: `{name}` is {t.dtype}; {METRICS_SUPPORTED}")
+    if t.requires_grad:
+        raise RuntimeError(f"orv_amd.ops: `{name}` requires grad; frame_metrics has no backward; {METRICS_SUPPORTED}")
+    if t.dim() != 4 or t.shape[3] != 3:
+        raise ValueError(f"orv_amd.ops: `{name}` must be [N, H, W, 3] (a view of any strides) with 3 channels (got {tuple(t.shape)}); {METRICS_SUPPORTED}")
+    storage = t.untyped_storage()
+    f = Frames()
+    f.data, f.kind, f.h, f.w = storage.data_ptr(), 0 if t.dtype == torch.float32 else 1, t.shape[1], t.shape[2]
+    f.extent, f.offset = storage.nbytes() // t.element_size(), t.storage_offset()
+    for k in range(4):
+        f.stride[k] = t.stride(k)
+    return f
+
+
+def frame_metrics(pred, gt, size, data_range: float = 1.0, full: bool = False):
+    """pred, gt: uint8 (divided by 255) or fp32 [N, H, W, 3] views of any strides, each with its own H and W; both are resized to
+    ``size`` = (h, w) by the bilinear rule of DESIGN.md §16 -> fp64 [3, N] = (mse, psnr, ssim) per frame, and with ``full`` the fp32
+    SSIM map [N, h - 6, w - 6, 3]."""
+    fp, fg = _frames_desc(pred, "pred"), _frames_desc(gt, "gt")
+    _same_device((pred, "pred"), (gt, "gt"))
+    if pred.shape[0] != gt.shape[0]:
+        raise ValueError(f"orv_amd.ops: `pred` has {pred.shape[0]} frames and `gt` has {gt.shape[0]}; supported: the same number of frames")
+    h, w = (int(v) for v in size)
+    if h < 7 or w < 7:
+        raise ValueError(f"orv_amd.ops: size = {(h, w)}; supported: a resized height and width of at least 7 (one 7 x 7 window)")
+    N = pred.shape[0]
+    out = torch.empty(3, N, dtype=torch.float64, device=pred.device)
+    ssim_map = torch.empty(N, h - 6, w - 6, 3, dtype=torch.float32, device=pred.device) if full else None
+    nbytes = lib().orv_frame_metrics_workspace(N, h, w)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=pred.device)
+    with _timed(("frame_metrics", fp.kind, fg.kind, N, fp.h, fp.w, fg.h, fg.w, h, w, int(full))):
+        check(lib().orv_frame_metrics(ctypes.byref(fp), ctypes.byref(fg), N, h, w, float(data_range), _p(out), _p(ssim_map), _p(ws), nbytes,
+                                      _stream()), "orv_frame_metrics")
+    return out, ssim_map
