@@ -665,6 +665,57 @@ long orv_frame_metrics_workspace(int N, int h, int w);
 int orv_frame_metrics(const orv_frames_t* pred, const orv_frames_t* gt, int N, int h, int w, double data_range, double* out,
                       float* ssim_map, void* workspace, long workspace_bytes, void* stream);
 
+/* -- Point-cloud cleaning and normals: the front of ORV's reconstruction stage -----------------------------------------------------------
+ * Replaces the per-frame CPU work of get_dense_points (orv/dataset/prepare_dataset.py:786-875) between the .ply points and NKSR's two
+ * input tensors (:754-755): _preprocess_points (:806-822: z < 0.6, then Open3D's remove_statistical_outlier(30, 1.5)) and
+ * process_nksr._preprocess_point_cloud (:729-741: estimate_normals(KDTreeSearchParamKNN(20)), orient_normals_towards_camera_location()).
+ * The arithmetic contract.  PARITY UNPINNED: Open3D is not installed where this was written and has no ROCm path;
+ * its semantics are restated from memory and the kernels are held to this restatement.
+ *   points   fp32 [N, 3], contiguous; every distance is fp64 on the fp32 values widened exactly.
+ *   kNN      d2(i, j) = (dx dx + dy dy) + dz dz with dx = (double)p_j.x - (double)p_i.x ..., every product and sum rounded to fp64 on its
+ *            own (no FMA).  The neighbours of i are the k' = min(k, N) points of smallest (d2, index), in that order; i itself is a
+ *            candidate at d2 = 0; a tie in d2 goes to the smaller index.  1 <= k <= 64.  idx int32 [N, k'], d2 fp64 [N, k'], ascending.
+ *   outliers avg_i = (sum over the ranks, in rank order, of sqrt(d2[i, r])) / k'.  Over the V points with avg_i > 0: mean = sum / V,
+ *            std = sqrt(sum (avg_i - mean)^2 / (V - 1)), thr = mean + std_ratio std; i is kept iff avg_i > 0 and avg_i < thr.  V == 0
+ *            makes mean NaN and V == 1 makes std NaN: both keep nothing.  Both sums in a fixed two-stage order.
+ *   normals  k' < 3 gives (0, 0, 1).  Else m = the neighbours' mean (fp64, rank order), C = sum (p - m)(p - m)^T / k' (the centred
+ *            two-pass form), the normal a unit eigenvector of C's smallest eigenvalue (analytic, fp64); C == 0 gives (0, 0, 1); for a
+ *            rank-1 C with line direction u the normal is e x u normalised, e the coordinate axis of the smallest |u| component.  Then
+ *            v = camera - p and the normal is negated when (n.x v.x + n.y v.y) + n.z v.z < 0.  One rounding to fp32, at the store.
+ * A search is four calls around one torch step: cells -> stable sort of the keys -> cell_table -> knn -> knn_brute on the queries knn
+ * flagged.  The grid is (x0, y0, z0) + cell * [0, gx) x [0, gy) x [0, gz), at most 2^24 cells; cell coordinates floor((p - lo) / cell) in
+ * fp64 are clamped to it, so the result does not depend on the grid - only the time does.  No atomics: bit-reproducible.  Every entry
+ * point validates its arguments before any launch; N = 0 launches nothing.
+ *
+ * Per point, the key (z gy + y) gx + x of its clamped cell (replaces the KD-tree build of :737 and of remove_statistical_outlier, :819). */
+int orv_pc_cells(const float* points, int N, float x0, float y0, float z0, double cell, int gx, int gy, int gz, long* keys, void* stream);
+/* On the stably sorted keys with order [N] int64 = the point of each sorted entry (the rest of the KD-tree build, :737, :819):
+ * start int32 [n_cells + 1] = the first sorted position of every cell (start[n_cells] = N), sorted_points fp32 [N, 3] = the points in
+ * sorted order, so that a cell's points are contiguous. */
+int orv_pc_cell_table(const long* sorted_keys, const long* order, const float* points, int N, int n_cells, int* start, float* sorted_points,
+                      void* stream);
+/* The k-nearest-neighbour search (replaces the KD-tree queries behind remove_statistical_outlier, :819, and KDTreeSearchParamKNN, :737).
+ * One wave per query with the running list one entry per lane; the cubes of cells of ring 0..3 around the query's cell are walked until
+ * the list is full and its last d2 is below the squared distance to every face of the cube that is not on the grid's border.  Rows of
+ * finished queries are written to idx / d2 [N, k']; pending uint8 [N] = 1 for the others, which orv_pc_knn_brute must finish. */
+int orv_pc_knn(const float* sorted_points, const long* order, const int* start, int N, int k, float x0, float y0, float z0, double cell,
+               int gx, int gy, int gz, int* idx, double* d2, unsigned char* pending, void* stream);
+/* The same search (:819, :737) for the Q listed queries (int64 point numbers) by a scan of all N points, one workgroup per query: what
+ * keeps the result exact for every input and every cell edge. */
+int orv_pc_knn_brute(const float* points, int N, int k, const long* queries, int Q, int* idx, double* d2, void* stream);
+/* Statistical outlier removal on the search's d2 [N, k'] (replaces remove_statistical_outlier(nb_neighbors=30, std_ratio=1.5), :819):
+ * avg fp64 [N], stats fp64 [4] = mean, std, thr, V, keep uint8 [N]; workspace = orv_pc_outlier_workspace(N) bytes, 8-byte aligned.  Six
+ * launches: avg, then twice (partial sums per 1024 points, one workgroup summing the partials in order), then the mask. */
+long orv_pc_outlier_workspace(int N);
+int orv_pc_outlier(const double* d2, int N, int k, double std_ratio, double* avg, double* stats, unsigned char* keep, void* workspace,
+                   long workspace_bytes, void* stream);
+/* Normals from the search's idx [N, k'] (replaces estimate_normals(KDTreeSearchParamKNN(20)) and
+ * orient_normals_towards_camera_location(), :737-738): normals fp32 [N, 3], oriented towards the camera location.  One thread per point. */
+int orv_pc_normals(const float* points, const int* idx, int N, int k, double camx, double camy, double camz, float* normals, void* stream);
+/* The standalone orientation (orient_normals_towards_camera_location(), :738) of given normals [N, 3] into out [N, 3], in fp64: a zero
+ * normal becomes (camera - p) / |camera - p|, or (0, 0, 1) when that is zero too; any other is negated when n . (camera - p) < 0. */
+int orv_pc_orient(const float* points, const float* normals, int N, double camx, double camy, double camz, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

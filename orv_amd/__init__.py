@@ -30,4 +30,8 @@ def __getattr__(name):
     if name in ("frame_metrics", "psnr_ssim", "frechet_distance"):
         from . import metrics
         return getattr(metrics, name)
+    # the point-cloud front of the reconstruction stage (orv_amd/pointcloud.py), resolved on first use likewise
+    if name in ("remove_statistical_outlier", "estimate_normals", "orient_normals_towards_camera_location", "preprocess_points", "nksr_inputs"):
+        from . import pointcloud
+        return getattr(pointcloud, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

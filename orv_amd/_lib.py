@@ -158,6 +158,14 @@ SIGNATURES = {
                                  c_void_p, c_int, c_void_p]),
     "orv_frame_metrics_workspace": (c_long, [c_int, c_int, c_int]),
     "orv_frame_metrics": (c_int, [POINTER(Frames), POINTER(Frames), c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "orv_pc_cells": (c_int, [c_void_p, c_int] + [c_float] * 3 + [c_double] + [c_int] * 3 + [c_void_p, c_void_p]),
+    "orv_pc_cell_table": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 3),
+    "orv_pc_knn": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_float] * 3 + [c_double] + [c_int] * 3 + [c_void_p] * 4),
+    "orv_pc_knn_brute": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int] + [c_void_p] * 3),
+    "orv_pc_outlier_workspace": (c_long, [c_int]),
+    "orv_pc_outlier": (c_int, [c_void_p, c_int, c_int, c_double] + [c_void_p] * 4 + [c_long, c_void_p]),
+    "orv_pc_normals": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_double] * 3 + [c_void_p, c_void_p]),
+    "orv_pc_orient": (c_int, [c_void_p, c_void_p, c_int] + [c_double] * 3 + [c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1094,3 +1094,115 @@ def frame_metrics(pred, gt, size, data_range: float = 1.0, full: bool = False):
         check(lib().orv_frame_metrics(ctypes.byref(fp), ctypes.byref(fg), N, h, w, float(data_range), _p(out), _p(ssim_map), _p(ws), nbytes,
                                       _stream()), "orv_frame_metrics")
     return out, ssim_map
+
+
+# ---- point-cloud cleaning and normals (csrc/pointcloud.hip) ----
+def _pc_points(points, who):
+    _need_c(points, torch.float32, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{who}: points must be [N,3] (got {tuple(points.shape)})")
+    return points.shape[0]
+
+
+def _pc_grid(origin, cell, dims):
+    return [float(v) for v in origin] + [float(cell)] + [int(g) for g in dims]
+
+
+def pc_cells(points, origin, cell, dims):
+    """-> keys int64 [N]: the linear key of every point's clamped cell on the grid ``origin`` [3] + ``cell`` * ``dims`` [3] (gx, gy, gz)."""
+    N = _pc_points(points, "pc_cells")
+    keys = torch.empty(N, dtype=torch.int64, device=points.device)
+    with _timed(("pc_cells", N)):
+        check(lib().orv_pc_cells(_p(points), N, *_pc_grid(origin, cell, dims), _p(keys), _stream()), "orv_pc_cells")
+    return keys
+
+
+def pc_cell_table(sorted_keys, order, points, n_cells):
+    """-> (start int32 [n_cells + 1], sorted_points fp32 [N,3]) of the stably sorted keys; ``order`` = the sort's int64 indices."""
+    N = _pc_points(points, "pc_cell_table")
+    _need_c(sorted_keys, torch.int64, "sorted_keys"), _need_c(order, torch.int64, "order")
+    _same_device((points, "points"), (sorted_keys, "sorted_keys"), (order, "order"))
+    if sorted_keys.numel() != N or order.numel() != N:
+        raise ValueError("pc_cell_table: sorted_keys [N], order [N], points [N,3]")
+    start = torch.full((int(n_cells) + 1,), N, dtype=torch.int32, device=points.device)
+    spts = torch.empty(N, 3, dtype=torch.float32, device=points.device)
+    with _timed(("pc_cell_table", N, int(n_cells))):
+        check(lib().orv_pc_cell_table(_p(sorted_keys), _p(order), _p(points), N, int(n_cells), _p(start), _p(spts), _stream()), "orv_pc_cell_table")
+    return start, spts
+
+
+def _pc_out(N, k, device):
+    kk = min(int(k), N)
+    return torch.empty(N, max(kk, 0), dtype=torch.int32, device=device), torch.empty(N, max(kk, 0), dtype=torch.float64, device=device)
+
+
+def pc_knn(sorted_points, order, start, k, origin, cell, dims, out=None):
+    """The grid walk -> (idx int32 [N, k'], d2 fp64 [N, k'], pending uint8 [N]); rows with pending = 1 are left to ``pc_knn_brute``."""
+    N = _pc_points(sorted_points, "pc_knn")
+    _need_c(order, torch.int64, "order"), _need_c(start, torch.int32, "start")
+    _same_device((sorted_points, "sorted_points"), (order, "order"), (start, "start"))
+    dims = [int(g) for g in dims]
+    if order.numel() != N or start.numel() != dims[0] * dims[1] * dims[2] + 1:
+        raise ValueError("pc_knn: sorted_points [N,3], order [N], start [gx * gy * gz + 1]")
+    idx, d2 = out if out is not None else _pc_out(N, k, order.device)
+    pending = torch.empty(N, dtype=torch.uint8, device=order.device)
+    with _timed(("pc_knn", N, int(k), *dims)):
+        check(lib().orv_pc_knn(_p(sorted_points), _p(order), _p(start), N, int(k), *_pc_grid(origin, cell, dims), _p(idx), _p(d2), _p(pending),
+                               _stream()), "orv_pc_knn")
+    return idx, d2, pending
+
+
+def pc_knn_brute(points, k, queries, out=None):
+    """The scan of all points for the int64 point numbers in ``queries`` [Q] -> (idx, d2) [N, k'] with those rows written (into ``out`` when given)."""
+    N = _pc_points(points, "pc_knn_brute")
+    _need_c(queries, torch.int64, "queries")
+    _same_device((points, "points"), (queries, "queries"))
+    idx, d2 = out if out is not None else _pc_out(N, k, points.device)
+    _need_c(idx, torch.int32, "idx"), _need_c(d2, torch.float64, "d2")
+    if idx.shape != (N, min(int(k), N)) or d2.shape != idx.shape:
+        raise ValueError("pc_knn_brute: idx and d2 must be [N, min(k, N)]")
+    with _timed(("pc_knn_brute", N, int(k), queries.numel())):
+        check(lib().orv_pc_knn_brute(_p(points), N, int(k), _p(queries), queries.numel(), _p(idx), _p(d2), _stream()), "orv_pc_knn_brute")
+    return idx, d2
+
+
+def pc_outlier(d2, k, std_ratio):
+    """d2 fp64 [N, k'] of a search with ``k`` -> (avg fp64 [N], stats fp64 [4] = mean, std, thr, V, keep uint8 [N])."""
+    _need_c(d2, torch.float64, "d2")
+    if d2.dim() != 2 or d2.shape[1] != min(int(k), d2.shape[0]):
+        raise ValueError(f"pc_outlier: d2 must be [N, min(k, N)] (got {tuple(d2.shape)} at k = {k})")
+    N, dev = d2.shape[0], d2.device
+    avg, keep = torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
+    stats = torch.full((4,), float("nan"), dtype=torch.float64, device=dev)
+    if N == 0:
+        stats[3] = 0.0
+    nbytes = lib().orv_pc_outlier_workspace(N)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+    with _timed(("pc_outlier", N, int(k))):
+        check(lib().orv_pc_outlier(_p(d2), N, int(k), float(std_ratio), _p(avg), _p(stats), _p(keep), _p(ws), nbytes, _stream()), "orv_pc_outlier")
+    return avg, stats, keep
+
+
+def pc_normals(points, idx, k, camera):
+    """idx int32 [N, k'] of a search with ``k`` -> normals fp32 [N,3], oriented towards ``camera`` [3]."""
+    N = _pc_points(points, "pc_normals")
+    _need_c(idx, torch.int32, "idx")
+    _same_device((points, "points"), (idx, "idx"))
+    if idx.shape != (N, min(int(k), N)):
+        raise ValueError(f"pc_normals: idx must be [N, min(k, N)] (got {tuple(idx.shape)} at k = {k})")
+    normals = torch.empty(N, 3, dtype=torch.float32, device=points.device)
+    with _timed(("pc_normals", N, int(k))):
+        check(lib().orv_pc_normals(_p(points), _p(idx), N, int(k), *[float(c) for c in camera], _p(normals), _stream()), "orv_pc_normals")
+    return normals
+
+
+def pc_orient(points, normals, camera):
+    """-> normals fp32 [N,3] turned towards ``camera`` [3]; a zero normal becomes the unit vector to the camera, or (0, 0, 1)."""
+    N = _pc_points(points, "pc_orient")
+    _need_c(normals, torch.float32, "normals")
+    _same_device((points, "points"), (normals, "normals"))
+    if normals.shape != points.shape:
+        raise ValueError(f"pc_orient: normals must be [N,3] like points (got {tuple(normals.shape)})")
+    out = torch.empty_like(normals)
+    check(lib().orv_pc_orient(_p(points), _p(normals), N, *[float(c) for c in camera], _p(out), _stream()), "orv_pc_orient")
+    return out
