@@ -394,6 +394,11 @@ float orv_attention_static_limit(int aligned_out);
  * softmax forms are launched; the workgroups of the one the scalar does not select exit at once. */
 int orv_attention_fwd_bounded_dev(const void* qkv, int ld_qkv, void* out, int ld_out, float* lse, int B, int S, int H, float scale,
                                   const float* score_bound_dev, void* stream);
+/* Developer switch, in the manner of orv_gemm_kernel_name: the kernel symbol(s) a forward-attention entry point launches for a call, spelled
+ * as in the source (two launches: joined by " + ").  Host arithmetic only, no GPU work.  entry: 0 orv_attention_fwd without vT, 1 with
+ * vT, 2 _bounded, 3 _packed, 4 _bounded_dev; aligned_out: ld_out % 8 == 0 and a 16-byte aligned out.  The opt-in key split of _bounded_ws
+ * depends on the caller's workspace and is not reported. */
+int orv_attention_kernel_name(int entry, int B, int S, int H, float scale, float score_bound, int aligned_out, char* buf, int len);
 
 /* -- T5 text encoder (orv_amd.t5.T5EncoderModel) ------------------------------------------------------------------------------------ */
 /* The reference encodes prompts with transformers' T5EncoderModel, `text_encoder(ids)[0]` (orv/models/text_encoder.py:34, called from

@@ -27,23 +27,23 @@ constexpr float RESCALE_THR = 8.f;  // defer the running-max update while exp2 a
 
 struct AttnArgs {
     const bf16_t* qkv; long ld;
-    const bf16_t* vT;
+    const bf16_t* vT = nullptr;
     bf16_t* out; long ld_out;
     float* lse;
-    int B, S, H, s_pad;
+    int B, S, H, s_pad = 0;
     float scale_log2;  // scale * log2(e)
     float scale;
-    float shift;       // STATIC kernels: fixed softmax shift in log2 units (>= every score the caller can produce)
+    float shift = 0.f; // STATIC kernels: fixed softmax shift in log2 units (>= every score the caller can produce)
     // orv_attention_fwd_bounded_dev: the score bound lives in device memory (training: it changes with every optimizer step and must
     // not cost a device -> host read).  Both softmax forms are launched; each workgroup reads the scalar and the form it does not
     // select returns at once (guard_dev == nullptr: no guard).
-    const float* guard_dev;
-    float guard_limit;
+    const float* guard_dev = nullptr;
+    float guard_limit = 0.f;
     // key-split tail of attn_fwd_pp_kernel<true, true> (orv_attention_fwd_bounded_ws): workgroups [0, n_full) are whole items; the
     // items from n_full on are cut into ks key ranges each (workgroup n_full + r * ks + part), whose unnormalised partial
     // outputs meet in ws_o / ws_l; ws_cnt[r] counts the arrivals of item r (zeroed by the launch function).
-    float* ws_o; float* ws_l; unsigned* ws_cnt;
-    int n_full, ks;
+    float* ws_o = nullptr; float* ws_l = nullptr; unsigned* ws_cnt = nullptr;
+    int n_full = 0, ks = 0;
     // orv_attention_fwd_packed: `out` is the P16 layout (include/orv_mi355.h orv_gemm_t) of the [B S, H 64] output, ld_out = H 64 - the A
     // operand of the out-projection GEMM (gemm_d8.hip) without a row-major copy in between.  attn_fwd_pp_kernel<true, false> only.
     int out_packed = 0;
@@ -1406,33 +1406,19 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
 
 }  // namespace
 
-extern "C" int orv_attention_fwd(const void* qkv, int ld_qkv, const void* vT, void* out, int ld_out, float* lse, int B,
-                                 int S, int H, int s_pad, float scale, void* stream) {
-    ORV_REQUIRE(qkv && out, "orv_attention_fwd: null operand");
-    ORV_REQUIRE(B > 0 && S > 0 && H > 0, "orv_attention_fwd: empty problem");
-    ORV_REQUIRE(!vT || (s_pad % 64 == 0 && s_pad >= S), "orv_attention_fwd: s_pad=%d must be a multiple of 64 and >= S=%d", s_pad, S);
-    ORV_REQUIRE(ld_qkv % 8 == 0 && ld_out % 4 == 0, "orv_attention_fwd: misaligned leading dimension");
-    AttnArgs a;
-    a.qkv = (const bf16_t*)qkv; a.ld = ld_qkv; a.vT = (const bf16_t*)vT; a.out = (bf16_t*)out; a.ld_out = ld_out;
-    a.lse = lse; a.B = B; a.S = S; a.H = H; a.s_pad = s_pad;
-    a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f; a.shift = 0.f; a.guard_dev = nullptr; a.guard_limit = 0.f; a.ws_o = a.ws_l = nullptr; a.ws_cnt = nullptr; a.n_full = a.ks = 0;
-    dim3 grid(((S + 255) / 256) * H * B);
-    // q pre-multiplied by scale*log2(e) in orv_qkv_prep (q_premul) arrives here as scale == 1/log2(e): fused fast path
-    const bool fused = fabsf(a.scale_log2 - 1.0f) < 1e-6f;
-    hipStream_t st = (hipStream_t)stream;
-    static int use_pp = -1;          // ORV_ATTN_PP=0: A/B switch (v2 instead of the ping-pong kernel)
-    if (use_pp < 0) { const char* e = getenv("ORV_ATTN_PP"); use_pp = (e && atoi(e) == 0) ? 0 : 1; }
-    if (!vT) {                       // V read in place from the packed projection (transposing LDS reads): the shipped path
-        if (fused && use_pp && ld_out % 8 == 0 && ((uintptr_t)out & 15) == 0)
-            hipLaunchKernelGGL((attn_fwd_pp_kernel<false>), grid, dim3(512), 0, st, a);
-        else if (fused) hipLaunchKernelGGL((attn_fwd_v2_kernel<true, true>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((attn_fwd_v2_kernel<true, false>), grid, dim3(512), 0, st, a);
-    } else if (fused) hipLaunchKernelGGL((attn_fwd_v1_kernel<true, true>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((attn_fwd_v1_kernel<true, false>), grid, dim3(512), 0, st, a);
-    return orv_check_launch("orv_attention_fwd");
-}
+// ---- Host dispatch.  Five entry points share ten kernel forms: attn_pick alone decides which form a call runs, attn_launch alone
+// launches it, and orv_attention_kernel_name reports the same decision without a GPU (tests/test_attention_plan_host.py pins it).
+struct AttnSwitches {      // process switches, read once
+    bool pp = orv_env_int("ORV_ATTN_PP", 1) != 0;                           // =0: the v2 kernel instead of the ping-pong kernel (A/B)
+    bool fixed = orv_env_int("ORV_ATTN_STATIC", 1) != 0;                    // =0: online softmax only (A/B)
+    bool m16 = orv_env_int("ORV_ATTN_M16", ORV_ATTN_M16_DEFAULT) != 0;      // =1: the 16x16x32 form of the ping-pong kernel (A/B)
+    bool w64 = orv_env_int("ORV_ATTN_W64", ORV_ATTN_W64_DEFAULT) != 0;      // =1: the 64-rows-per-wave kernel for the shift-free softmax (A/B)
+    bool split = orv_env_int("ORV_ATTN_SPLIT", 0) != 0;                     // =1: opt into the key-split tail (attn_split_plan)
+    int slots = orv_env_int("ORV_ATTN_SLOTS", 0);       // pretend the chip has this many workgroup slots (tests of the split path at small shapes)
+};
+static const AttnSwitches& attn_switches() { static const AttnSwitches sw{}; return sw; }
 
-// The same attention when the caller can BOUND the scores: |q . k| * scale * log2(e) <= score_bound for every (query, key) of the
+// When the caller can BOUND the scores: |q . k| * scale * log2(e) <= score_bound for every (query, key) of the
 // call (ORV: from the qk-LayerNorm affine parameters, orv_amd/cogvideox_control.py `score_bound`).  With the fused scale
 // (q pre-multiplied, scale == 1 / log2 e) the softmax then needs no running max:
 //   * attn_fwd_pp_kernel<STATIC> (16-byte aligned output) computes P = exp2(s) with NO shift at all, so P lies in
@@ -1440,48 +1426,122 @@ extern "C" int orv_attention_fwd(const void* qkv, int ld_qkv, const void* vT, vo
 //     (2^90 x 2^14 keys x 2^10 = 2^114 < 2^127; 2^-90 > 2^-126) - ORV_STATIC_LIMIT_PP.  At gamma = 1, beta = 0 the bound is
 //     11.8, so the limit admits max|gamma_q| max|gamma_k| up to ~7.6 (40 was exceeded from ~3.4).
 //   * attn_fwd_v2_kernel<.., STATIC> (unaligned outputs) shifts by the bound, P in [2^(-2 bound), 1]: valid to bound <= 60.
-// Above the limit this is orv_attention_fwd (online softmax).  A bound that does not hold gives wrong results and, far enough
+// Above the limit the online softmax runs.  A bound that does not hold gives wrong results and, far enough
 // off, inf: the caller owns the guarantee (tests/test_gpu_kernels.py exercises a violated bound to show it is a contract).
 constexpr float ORV_STATIC_LIMIT_PP = 90.f, ORV_STATIC_LIMIT_V2 = 60.f;
-// ORV_ATTN_W64: 1 = the 64-rows-per-wave kernel for the shift-free softmax, 0 = the 8-wave ping-pong kernel (A/B switch; default below)
-static bool attn_use_w64() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ORV_ATTN_W64"); v = e ? (atoi(e) != 0) : ORV_ATTN_W64_DEFAULT; }
-    return v != 0;
+// largest score bound (log2 units) the fixed-shift softmax accepts: 16-byte aligned output (ping-pong kernel) / any output (v2 kernel)
+extern "C" float orv_attention_static_limit(int aligned_out) { return aligned_out ? ORV_STATIC_LIMIT_PP : ORV_STATIC_LIMIT_V2; }
+
+// Key-split tail (orv_attention_fwd_bounded_ws).  The grid of the ping-pong kernel is ceil(S / 256) H B workgroups on 2 x CUs slots: at
+// the headline shape 1560 on 512 = 3.05 rounds, and the dispatcher's fourth "round" of 24 full-length workgroups costs ~10 % of the
+// launch (profiles/r3_attention_pingpong.txt: span 3.79 workgroup lifetimes against 3.43 for an exact 3-round shape).  Plan: the
+// items beyond the last full round - when they are few - are cut into ks key ranges each and dispatched last.
+struct AttnSplit { int n_full, rest, ks; };
+static int attn_items(int B, int S, int H) { return ((S + 255) / 256) * H * B; }     // one workgroup per 256 query rows of a (batch, head)
+static AttnSplit attn_split_plan(int B, int S, int H) {
+    AttnSplit sp{0, 0, 0};
+    // OPT-IN (ORV_ATTN_SPLIT=1).  Measured (profiles/r4_attention_key_split.txt): standalone 0.393 -> 0.364 ms per launch, but inside
+    // the graph-replayed step nothing (0.3215 vs 0.3231 ms, 41.1 ms / step either way, three interleaved rounds on one box) - and the
+    // split items sum their key ranges in another fp32 order, which a 30-block random-init model amplifies from 3e-5 per call to
+    // 1.1e-2 at the output, where the unsplit kernels make B = 4 bit-identical to four B = 1 calls.  Off by default.
+    if (!attn_switches().split) return sp;
+    int dev = 0, cus = 256; hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    const int slots = attn_switches().slots > 0 ? attn_switches().slots : 2 * cus, items = attn_items(B, S, H), nt = (S + KV - 1) / KV;
+    const int full = items / slots * slots, rest = items - full;
+    if (full == 0 || rest == 0 || rest * 4 > slots) return sp;          // nothing to cut, or the last round is not small
+    int ks = slots / (2 * rest) > 8 ? 8 : slots / (2 * rest);
+    while (ks > 1 && nt < 4 * ks) --ks;                                  // every part keeps at least 4 key tiles
+    if (ks < 2) return sp;
+    sp.n_full = full; sp.rest = rest; sp.ks = ks;
+    return sp;
 }
+// bytes of workspace orv_attention_fwd_bounded_ws wants for this shape (0: the shape is not split)
+static size_t attn_ws_bytes(const AttnSplit& sp) { return sp.ks ? 1024 + (size_t)sp.rest * sp.ks * (256 * 64 + 256) * sizeof(float) : 0; }
+extern "C" size_t orv_attention_ws_bytes(int B, int S, int H) { return attn_ws_bytes(attn_split_plan(B, S, H)); }
+
+enum AttnEntry { ATTN_FWD, ATTN_BOUNDED, ATTN_PACKED, ATTN_WS, ATTN_DEV };
+enum AttnForm { ATTN_PP_ONLINE, ATTN_V2_FUSED, ATTN_V2_PLAIN, ATTN_V1_FUSED, ATTN_V1_PLAIN,        // online softmax: attn_online
+                ATTN_W64, ATTN_M16, ATTN_PP_STATIC, ATTN_V2_STATIC, ATTN_PP_SPLIT, ATTN_DEV_PAIR };
+// one row per AttnForm, in its order: the symbol as the source spells it, and the kernel
+static const struct { const char* name; void (*kernel)(const AttnArgs); } ATTN_FORMS[] = {
+    {"attn_fwd_pp_kernel<false>", attn_fwd_pp_kernel<false>},
+    {"attn_fwd_v2_kernel<true, true>", attn_fwd_v2_kernel<true, true>},   {"attn_fwd_v2_kernel<true, false>", attn_fwd_v2_kernel<true, false>},
+    {"attn_fwd_v1_kernel<true, true>", attn_fwd_v1_kernel<true, true>},   {"attn_fwd_v1_kernel<true, false>", attn_fwd_v1_kernel<true, false>},
+    {"attn_fwd_w64_kernel", attn_fwd_w64_kernel},                         {"attn_fwd_m16_kernel", attn_fwd_m16_kernel},
+    {"attn_fwd_pp_kernel<true>", attn_fwd_pp_kernel<true>},               {"attn_fwd_v2_kernel<true, true, true>", attn_fwd_v2_kernel<true, true, true>},
+    {"attn_fwd_pp_kernel<true, true>", attn_fwd_pp_kernel<true, true>},
+    {"attn_fwd_pp_kernel<true> + attn_fwd_pp_kernel<false>", nullptr},      // ATTN_DEV_PAIR: two launches (attn_launch)
+};
+struct AttnPick { AttnForm form; int grid; };
+static bool attn_online(AttnForm f) { return f <= ATTN_V1_PLAIN; }
+// q pre-multiplied by scale*log2(e) in orv_qkv_prep (q_premul) arrives here as scale == 1/log2(e): fused fast path
+static bool attn_fused(float scale) { return fabsf(scale * 1.4426950408889634f - 1.0f) < 1e-6f; }
+
+// THE decision.  aligned_out: ld_out % 8 == 0 and a 16-byte aligned `out` (the ping-pong family stores 16 bytes per lane); items =
+// attn_items; sp: the split plan when the caller's workspace can hold it (ATTN_WS only), else ks = 0.  Kept as found, not fixed here:
+//   * ATTN_PACKED looks at W64 and M16 only, ORV_ATTN_PP=0 and ORV_ATTN_STATIC=0 do not reach it (its entry point has required the fused
+//     scale and 0 < bound <= 90); ATTN_DEV cannot test the bound on the host and has no M16 / W64 form;
+//   * ORV_ATTN_W64=1 does not disable the key split of ATTN_WS, though the unsplit call would run the w64 kernel.
+static AttnPick attn_pick(AttnEntry entry, bool has_vt, bool fused, bool aligned_out, float bound, const AttnSplit& sp, const AttnSwitches& sw, int items) {
+    const bool pp = sw.pp && aligned_out;
+    if (entry == ATTN_PACKED) return sw.w64 ? AttnPick{ATTN_W64, (items + 1) / 2} : AttnPick{sw.m16 ? ATTN_M16 : ATTN_PP_STATIC, items};
+    if (entry == ATTN_DEV && sw.fixed && pp && fused) return {ATTN_DEV_PAIR, items};
+    if (entry == ATTN_WS && sp.ks > 0 && sw.fixed && pp && !sw.m16 && fused && bound > 0.f && bound <= ORV_STATIC_LIMIT_PP)
+        return {ATTN_PP_SPLIT, sp.n_full + sp.rest * sp.ks};
+    if ((entry == ATTN_BOUNDED || entry == ATTN_WS) && sw.fixed && fused && bound > 0.f && bound <= (pp ? ORV_STATIC_LIMIT_PP : ORV_STATIC_LIMIT_V2)) {
+        if (!pp) return {ATTN_V2_STATIC, items};
+        return sw.w64 ? AttnPick{ATTN_W64, (items + 1) / 2} : AttnPick{sw.m16 ? ATTN_M16 : ATTN_PP_STATIC, items};
+    }
+    // online softmax: orv_attention_fwd, and every call the bounded entry points hand on to it (always without vT)
+    if (has_vt) return {fused ? ATTN_V1_FUSED : ATTN_V1_PLAIN, items};
+    if (!fused) return {ATTN_V2_PLAIN, items};
+    return {pp ? ATTN_PP_ONLINE : ATTN_V2_FUSED, items};        // V read in place from the packed projection: the shipped path
+}
+static AttnPick attn_plan(AttnEntry entry, bool has_vt, const void* out, long ld_out, int B, int S, int H, float scale, float bound, const AttnSplit& sp = {}) {
+    return attn_pick(entry, has_vt, attn_fused(scale), ld_out % 8 == 0 && orv_aligned(out, 16), bound, sp, attn_switches(), attn_items(B, S, H));
+}
+static int attn_launch(const AttnPick& pk, const AttnArgs& a, void* stream, const char* who) {       // who: the entry point, for the error text
+    hipStream_t st = (hipStream_t)stream;
+    auto go = [&](AttnForm f) { hipLaunchKernelGGL(ATTN_FORMS[f].kernel, dim3(pk.grid), dim3(512), 0, st, a); };
+    switch (pk.form) {
+    case ATTN_DEV_PAIR: go(ATTN_PP_STATIC); go(ATTN_PP_ONLINE); break;      // each workgroup of the form the device-side bound does not select returns at once
+    case ATTN_PP_SPLIT: if (hipMemsetAsync(a.ws_cnt, 0, 1024, st) != hipSuccess) { orv_set_error("%s: hipMemsetAsync failed", who); return ORV_EDEVICE; } [[fallthrough]];
+    default: go(pk.form);
+    }
+    return orv_check_launch(who);
+}
+// what every entry point sets; the rest (vT, shift, guard, workspace, packed output) keeps the defaults of AttnArgs unless its entry point sets it
+static AttnArgs attn_args(const void* qkv, int ld_qkv, void* out, long ld_out, float* lse, int B, int S, int H, float scale) {
+    AttnArgs a;
+    a.qkv = (const bf16_t*)qkv; a.ld = ld_qkv; a.out = (bf16_t*)out; a.ld_out = ld_out; a.lse = lse;
+    a.B = B; a.S = S; a.H = H; a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
+    return a;
+}
+
+extern "C" int orv_attention_fwd(const void* qkv, int ld_qkv, const void* vT, void* out, int ld_out, float* lse, int B,
+                                 int S, int H, int s_pad, float scale, void* stream) {
+    ORV_REQUIRE(qkv && out, "orv_attention_fwd: null operand");
+    ORV_REQUIRE(B > 0 && S > 0 && H > 0, "orv_attention_fwd: empty problem");
+    ORV_REQUIRE(!vT || (s_pad % 64 == 0 && s_pad >= S), "orv_attention_fwd: s_pad=%d must be a multiple of 64 and >= S=%d", s_pad, S);
+    ORV_REQUIRE(ld_qkv % 8 == 0 && ld_out % 4 == 0, "orv_attention_fwd: misaligned leading dimension");
+    AttnArgs a = attn_args(qkv, ld_qkv, out, ld_out, lse, B, S, H, scale);
+    a.vT = (const bf16_t*)vT; a.s_pad = s_pad;
+    return attn_launch(attn_plan(ATTN_FWD, vT != nullptr, out, ld_out, B, S, H, scale, 0.f), a, stream, "orv_attention_fwd");
+}
+
+// The same attention when the caller can BOUND the scores (ORV_STATIC_LIMIT_* above): the fixed-shift kernels where attn_pick admits
+// them, else orv_attention_fwd - which then also owns the validation, so errors of that path read "orv_attention_fwd: ...".
 extern "C" int orv_attention_fwd_bounded(const void* qkv, int ld_qkv, void* out, int ld_out, float* lse, int B, int S, int H,
                                          float scale, float score_bound, void* stream) {
-    const float scale_log2 = scale * 1.4426950408889634f;
-    const bool fused = fabsf(scale_log2 - 1.0f) < 1e-6f;
-    static int use_static = -1;      // ORV_ATTN_STATIC=0: A/B switch
-    if (use_static < 0) { const char* e = getenv("ORV_ATTN_STATIC"); use_static = (e && atoi(e) == 0) ? 0 : 1; }
-    static int use_pp_ = -1;
-    if (use_pp_ < 0) { const char* e = getenv("ORV_ATTN_PP"); use_pp_ = (e && atoi(e) == 0) ? 0 : 1; }
-    const bool aligned_out = ld_out % 8 == 0 && ((uintptr_t)out & 15) == 0;
-    const float limit = (use_pp_ && aligned_out) ? ORV_STATIC_LIMIT_PP : ORV_STATIC_LIMIT_V2;
-    if (!use_static || !fused || !(score_bound > 0.f) || score_bound > limit)
-        return orv_attention_fwd(qkv, ld_qkv, nullptr, out, ld_out, lse, B, S, H, 0, scale, stream);
+    const AttnPick pk = attn_plan(ATTN_BOUNDED, false, out, ld_out, B, S, H, scale, score_bound);
+    if (attn_online(pk.form)) return orv_attention_fwd(qkv, ld_qkv, nullptr, out, ld_out, lse, B, S, H, 0, scale, stream);
     ORV_REQUIRE(qkv && out, "orv_attention_fwd_bounded: null operand");
     ORV_REQUIRE(B > 0 && S > 0 && H > 0, "orv_attention_fwd_bounded: empty problem");
     ORV_REQUIRE(ld_qkv % 8 == 0 && ld_out % 4 == 0, "orv_attention_fwd_bounded: misaligned leading dimension");
-    AttnArgs a;
-    a.qkv = (const bf16_t*)qkv; a.ld = ld_qkv; a.vT = nullptr; a.out = (bf16_t*)out; a.ld_out = ld_out;
-    a.lse = lse; a.B = B; a.S = S; a.H = H; a.s_pad = 0;
-    a.scale = scale; a.scale_log2 = scale_log2; a.shift = score_bound; a.guard_dev = nullptr; a.guard_limit = 0.f; a.ws_o = a.ws_l = nullptr; a.ws_cnt = nullptr; a.n_full = a.ks = 0;
-    dim3 grid(((S + 255) / 256) * H * B);
-    static int use_pp = -1;
-    if (use_pp < 0) { const char* e = getenv("ORV_ATTN_PP"); use_pp = (e && atoi(e) == 0) ? 0 : 1; }
-    static int use_m16 = -1;         // ORV_ATTN_M16=1: the 16x16x32 form of the ping-pong kernel (A/B switch)
-    if (use_m16 < 0) { const char* e = getenv("ORV_ATTN_M16"); use_m16 = e ? (atoi(e) != 0) : ORV_ATTN_M16_DEFAULT; }
-    if (use_pp && attn_use_w64() && ld_out % 8 == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL(attn_fwd_w64_kernel, dim3((grid.x + 1) / 2), dim3(512), 0, (hipStream_t)stream, a);
-    else if (use_pp && use_m16 && ld_out % 8 == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL(attn_fwd_m16_kernel, grid, dim3(512), 0, (hipStream_t)stream, a);
-    else if (use_pp && ld_out % 8 == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL((attn_fwd_pp_kernel<true>), grid, dim3(512), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((attn_fwd_v2_kernel<true, true, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
-    return orv_check_launch("orv_attention_fwd_bounded");
+    AttnArgs a = attn_args(qkv, ld_qkv, out, ld_out, lse, B, S, H, scale);
+    a.shift = score_bound;
+    return attn_launch(pk, a, stream, "orv_attention_fwd_bounded");
 }
 
 // orv_attention_fwd_bounded with the output in the packed P16 layout (orv_gemm_t.a_packed of the out-projection, cogvideox_control.py:263).
@@ -1489,120 +1549,57 @@ extern "C" int orv_attention_fwd_bounded(const void* qkv, int ld_qkv, void* out,
 // output + the row-major GEMM).  `out` holds orv_packed_rows(B S) x (H 64) bf16.
 extern "C" int orv_attention_fwd_packed(const void* qkv, int ld_qkv, void* out, float* lse, int B, int S, int H, float scale, float score_bound,
                                         void* stream) {
-    const float scale_log2 = scale * 1.4426950408889634f;
     ORV_REQUIRE(qkv && out, "orv_attention_fwd_packed: null operand");
     ORV_REQUIRE(B > 0 && S > 0 && H > 0, "orv_attention_fwd_packed: empty problem");
-    ORV_REQUIRE(ld_qkv % 8 == 0 && ((uintptr_t)out & 15) == 0, "orv_attention_fwd_packed: misaligned operand");
-    ORV_REQUIRE(fabsf(scale_log2 - 1.0f) < 1e-6f && score_bound > 0.f && score_bound <= ORV_STATIC_LIMIT_PP,
+    ORV_REQUIRE(ld_qkv % 8 == 0 && orv_aligned(out, 16), "orv_attention_fwd_packed: misaligned operand");
+    ORV_REQUIRE(attn_fused(scale) && score_bound > 0.f && score_bound <= ORV_STATIC_LIMIT_PP,
                 "orv_attention_fwd_packed: needs the fused scale (scale * log2 e == 1) and 0 < score_bound <= %g (got scale %g bound %g)",
                 (double)ORV_STATIC_LIMIT_PP, (double)scale, (double)score_bound);
-    AttnArgs a;
-    a.qkv = (const bf16_t*)qkv; a.ld = ld_qkv; a.vT = nullptr; a.out = (bf16_t*)out; a.ld_out = (long)H * 64;
-    a.lse = lse; a.B = B; a.S = S; a.H = H; a.s_pad = 0;
-    a.scale = scale; a.scale_log2 = scale_log2; a.shift = score_bound; a.guard_dev = nullptr; a.guard_limit = 0.f; a.ws_o = a.ws_l = nullptr; a.ws_cnt = nullptr; a.n_full = a.ks = 0;
-    a.out_packed = 1;
-    static int use_m16p = -1;
-    if (use_m16p < 0) { const char* e = getenv("ORV_ATTN_M16"); use_m16p = e ? (atoi(e) != 0) : ORV_ATTN_M16_DEFAULT; }
-    if (attn_use_w64()) hipLaunchKernelGGL(attn_fwd_w64_kernel, dim3((((S + 255) / 256) * H * B + 1) / 2), dim3(512), 0, (hipStream_t)stream, a);
-    else if (use_m16p) hipLaunchKernelGGL(attn_fwd_m16_kernel, dim3(((S + 255) / 256) * H * B), dim3(512), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((attn_fwd_pp_kernel<true>), dim3(((S + 255) / 256) * H * B), dim3(512), 0, (hipStream_t)stream, a);
-    return orv_check_launch("orv_attention_fwd_packed");
+    AttnArgs a = attn_args(qkv, ld_qkv, out, (long)H * 64, lse, B, S, H, scale);
+    a.shift = score_bound; a.out_packed = 1;
+    return attn_launch(attn_plan(ATTN_PACKED, false, out, H * 64, B, S, H, scale, score_bound), a, stream, "orv_attention_fwd_packed");
 }
 
-// Key-split tail (orv_attention_fwd_bounded_ws).  The grid of the ping-pong kernel is ceil(S / 256) H B workgroups on 2 x CUs slots: at
-// the headline shape 1560 on 512 = 3.05 rounds, and the dispatcher's fourth "round" of 24 full-length workgroups costs ~10 % of the
-// launch (profiles/r3_attention_pingpong.txt: span 3.79 workgroup lifetimes against 3.43 for an exact 3-round shape).  Plan: the
-// items beyond the last full round - when they are few - are cut into ks key ranges each and dispatched last.
-struct AttnSplit { int n_full, rest, ks; };
-static AttnSplit attn_split_plan(int B, int S, int H) {
-    AttnSplit sp{0, 0, 0};
-    // OPT-IN (ORV_ATTN_SPLIT=1).  Measured (profiles/r4_attention_key_split.txt): standalone 0.393 -> 0.364 ms per launch, but inside
-    // the graph-replayed step nothing (0.3215 vs 0.3231 ms, 41.1 ms / step either way, three interleaved rounds on one box) - and the
-    // split items sum their key ranges in another fp32 order, which a 30-block random-init model amplifies from 3e-5 per call to
-    // 1.1e-2 at the output, where the unsplit kernels make B = 4 bit-identical to four B = 1 calls.  Off by default.
-    static int enabled = -1;
-    if (enabled < 0) { const char* e = getenv("ORV_ATTN_SPLIT"); enabled = (e && atoi(e) != 0) ? 1 : 0; }
-    if (!enabled) return sp;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    static int slots_env = -1;       // ORV_ATTN_SLOTS: pretend the chip has this many workgroup slots (tests of the split path at small shapes)
-    if (slots_env < 0) { const char* e = getenv("ORV_ATTN_SLOTS"); slots_env = e ? atoi(e) : 0; }
-    const int slots = slots_env > 0 ? slots_env : 2 * cus, items = ((S + 255) / 256) * H * B, nt = (S + KV - 1) / KV;
-    const int full = items / slots * slots, rest = items - full;
-    if (full == 0 || rest == 0 || rest * 4 > slots) return sp;          // nothing to cut, or the last round is not small
-    int ks = slots / (2 * rest);
-    if (ks > 8) ks = 8;
-    while (ks > 1 && nt < 4 * ks) --ks;                                  // every part keeps at least 4 key tiles
-    if (ks < 2) return sp;
-    sp.n_full = full; sp.rest = rest; sp.ks = ks;
-    return sp;
-}
-// bytes of workspace orv_attention_fwd_bounded_ws wants for this shape (0: the shape is not split)
-extern "C" size_t orv_attention_ws_bytes(int B, int S, int H) {
-    const AttnSplit sp = attn_split_plan(B, S, H);
-    if (!sp.ks) return 0;
-    return 1024 + (size_t)sp.rest * sp.ks * (256 * 64 + 256) * sizeof(float);
-}
-
-// largest score bound (log2 units) the fixed-shift softmax of orv_attention_fwd_bounded(_dev) accepts: 16-byte aligned output
-// (ping-pong kernel) / any output (v2 kernel)
-extern "C" float orv_attention_static_limit(int aligned_out) { return aligned_out ? ORV_STATIC_LIMIT_PP : ORV_STATIC_LIMIT_V2; }
-
-// orv_attention_fwd_bounded with a caller-provided workspace (>= orv_attention_ws_bytes(B, S, H), 256-byte aligned; reusable across
-// calls on one stream): when the fixed-shift ping-pong kernel applies and the shape has a small last round, that round is key-split
-// (above).  Without workspace, or where the plan does not apply, this IS orv_attention_fwd_bounded.  Results are deterministic
-// (fixed part order) but differ in fp32 summation order from the unsplit kernel for the split items.
+// orv_attention_fwd_bounded with a caller-provided workspace (>= orv_attention_ws_bytes(B, S, H), 256-byte aligned; reusable across calls on
+// one stream): a small last round of the fixed-shift ping-pong kernel is key-split (above).  Without workspace, or where the plan does not apply,
+// this IS orv_attention_fwd_bounded.  Results are deterministic (fixed part order) but differ in fp32 summation order for the split items.
 extern "C" int orv_attention_fwd_bounded_ws(const void* qkv, int ld_qkv, void* out, int ld_out, float* lse, int B, int S, int H,
                                             float scale, float score_bound, void* ws, size_t ws_bytes, void* stream) {
-    const float scale_log2 = scale * 1.4426950408889634f;
-    const bool fused = fabsf(scale_log2 - 1.0f) < 1e-6f;
-    static int use_static = -1, use_pp = -1, use_m16 = -1;
-    if (use_static < 0) { const char* e = getenv("ORV_ATTN_STATIC"); use_static = (e && atoi(e) == 0) ? 0 : 1; }
-    if (use_pp < 0) { const char* e = getenv("ORV_ATTN_PP"); use_pp = (e && atoi(e) == 0) ? 0 : 1; }
-    if (use_m16 < 0) { const char* e = getenv("ORV_ATTN_M16"); use_m16 = e ? (atoi(e) != 0) : ORV_ATTN_M16_DEFAULT; }
-    const AttnSplit sp = (ws && B > 0 && S > 0 && H > 0) ? attn_split_plan(B, S, H) : AttnSplit{0, 0, 0};
-    if (!sp.ks || !use_static || !use_pp || use_m16 || !fused || !(score_bound > 0.f) || score_bound > ORV_STATIC_LIMIT_PP ||
-        ld_out % 8 != 0 || ((uintptr_t)out & 15) != 0 || ((uintptr_t)ws & 255) != 0 || ws_bytes < orv_attention_ws_bytes(B, S, H))
-        return orv_attention_fwd_bounded(qkv, ld_qkv, out, ld_out, lse, B, S, H, scale, score_bound, stream);
+    AttnSplit sp = (ws && B > 0 && S > 0 && H > 0) ? attn_split_plan(B, S, H) : AttnSplit{0, 0, 0};
+    if (!orv_aligned(ws, 256) || ws_bytes < attn_ws_bytes(sp)) sp = AttnSplit{0, 0, 0};         // no usable workspace: no split
+    const AttnPick pk = attn_plan(ATTN_WS, false, out, ld_out, B, S, H, scale, score_bound, sp);
+    if (pk.form != ATTN_PP_SPLIT) return orv_attention_fwd_bounded(qkv, ld_qkv, out, ld_out, lse, B, S, H, scale, score_bound, stream);
     ORV_REQUIRE(qkv && out, "orv_attention_fwd_bounded_ws: null operand");
     ORV_REQUIRE(ld_qkv % 8 == 0, "orv_attention_fwd_bounded_ws: misaligned leading dimension");
-    AttnArgs a;
-    a.qkv = (const bf16_t*)qkv; a.ld = ld_qkv; a.vT = nullptr; a.out = (bf16_t*)out; a.ld_out = ld_out;
-    a.lse = lse; a.B = B; a.S = S; a.H = H; a.s_pad = 0;
-    a.scale = scale; a.scale_log2 = scale_log2; a.shift = 0.f; a.guard_dev = nullptr; a.guard_limit = 0.f;
-    a.ws_cnt = (unsigned*)ws;
-    a.ws_o = (float*)((char*)ws + 1024);
-    a.ws_l = a.ws_o + (size_t)sp.rest * sp.ks * 256 * 64;
-    a.n_full = sp.n_full; a.ks = sp.ks;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 1024, st) != hipSuccess) { orv_set_error("orv_attention_fwd_bounded_ws: hipMemsetAsync failed"); return ORV_EDEVICE; }
-    hipLaunchKernelGGL((attn_fwd_pp_kernel<true, true>), dim3(sp.n_full + sp.rest * sp.ks), dim3(512), 0, st, a);
-    return orv_check_launch("orv_attention_fwd_bounded_ws");
+    AttnArgs a = attn_args(qkv, ld_qkv, out, ld_out, lse, B, S, H, scale);
+    a.ws_cnt = (unsigned*)ws; a.ws_o = (float*)((char*)ws + 1024);            // (the counters are zeroed by attn_launch)
+    a.ws_l = a.ws_o + (size_t)sp.rest * sp.ks * 256 * 64; a.n_full = sp.n_full; a.ks = sp.ks;
+    return attn_launch(pk, a, stream, "orv_attention_fwd_bounded_ws");
 }
 
-// orv_attention_fwd_bounded with the bound in DEVICE memory (one fp32, e.g. element l of the per-layer bound vector the training
-// step recomputes on the device after every optimizer update): no device -> host read.  The fixed-shift and the online form of
-// the ping-pong kernel are both launched and every workgroup of the form the scalar does not select returns at once (~2 us of an
-// empty grid per call).  Needs the fused scale and a 16-byte aligned output (else: orv_attention_fwd, online softmax).
+// orv_attention_fwd_bounded with the bound in DEVICE memory (one fp32, e.g. element l of the per-layer bound vector the training step recomputes
+// on the device after every optimizer update): no device -> host read.  The fixed-shift and the online form of the ping-pong kernel are both launched
+// (~2 us of an empty grid per call).  Needs the fused scale and a 16-byte aligned output (else: orv_attention_fwd, online softmax).
 extern "C" int orv_attention_fwd_bounded_dev(const void* qkv, int ld_qkv, void* out, int ld_out, float* lse, int B, int S, int H,
                                              float scale, const float* score_bound_dev, void* stream) {
     ORV_REQUIRE(qkv && out && score_bound_dev, "orv_attention_fwd_bounded_dev: null operand");
     ORV_REQUIRE(B > 0 && S > 0 && H > 0, "orv_attention_fwd_bounded_dev: empty problem");
     ORV_REQUIRE(ld_qkv % 8 == 0 && ld_out % 4 == 0, "orv_attention_fwd_bounded_dev: misaligned leading dimension");
-    const float scale_log2 = scale * 1.4426950408889634f;
-    const bool fused = fabsf(scale_log2 - 1.0f) < 1e-6f;
-    static int use_static = -1, use_pp = -1;
-    if (use_static < 0) { const char* e = getenv("ORV_ATTN_STATIC"); use_static = (e && atoi(e) == 0) ? 0 : 1; }
-    if (use_pp < 0) { const char* e = getenv("ORV_ATTN_PP"); use_pp = (e && atoi(e) == 0) ? 0 : 1; }
-    if (!use_static || !use_pp || !fused || ld_out % 8 != 0 || ((uintptr_t)out & 15) != 0)
-        return orv_attention_fwd(qkv, ld_qkv, nullptr, out, ld_out, lse, B, S, H, 0, scale, stream);
-    AttnArgs a;
-    a.qkv = (const bf16_t*)qkv; a.ld = ld_qkv; a.vT = nullptr; a.out = (bf16_t*)out; a.ld_out = ld_out;
-    a.lse = lse; a.B = B; a.S = S; a.H = H; a.s_pad = 0;
-    a.scale = scale; a.scale_log2 = scale_log2; a.shift = 0.f; a.guard_dev = score_bound_dev; a.guard_limit = ORV_STATIC_LIMIT_PP; a.ws_o = a.ws_l = nullptr; a.ws_cnt = nullptr; a.n_full = a.ks = 0;
-    dim3 grid(((S + 255) / 256) * H * B);
-    hipLaunchKernelGGL((attn_fwd_pp_kernel<true>), grid, dim3(512), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL((attn_fwd_pp_kernel<false>), grid, dim3(512), 0, (hipStream_t)stream, a);
-    return orv_check_launch("orv_attention_fwd_bounded_dev");
+    const AttnPick pk = attn_plan(ATTN_DEV, false, out, ld_out, B, S, H, scale, 0.f);
+    if (pk.form != ATTN_DEV_PAIR) return orv_attention_fwd(qkv, ld_qkv, nullptr, out, ld_out, lse, B, S, H, 0, scale, stream);
+    AttnArgs a = attn_args(qkv, ld_qkv, out, ld_out, lse, B, S, H, scale);
+    a.guard_dev = score_bound_dev; a.guard_limit = ORV_STATIC_LIMIT_PP;
+    return attn_launch(pk, a, stream, "orv_attention_fwd_bounded_dev");
+}
+
+// The kernel symbol(s) an entry point launches for a call, as the source spells them (rocprofv3 adds the defaulted template arguments): attn_pick
+// on the host alone, no GPU work.  entry: 0 orv_attention_fwd without vT, 1 with vT, 2 _bounded, 3 _packed, 4 _bounded_dev (not: _bounded_ws).
+extern "C" int orv_attention_kernel_name(int entry, int B, int S, int H, float scale, float score_bound, int aligned_out, char* buf, int len) {
+    static const AttnEntry entries[] = {ATTN_FWD, ATTN_FWD, ATTN_BOUNDED, ATTN_PACKED, ATTN_DEV};
+    ORV_REQUIRE(buf && len > 0 && entry >= 0 && entry <= 4 && B > 0 && S > 0 && H > 0, "orv_attention_kernel_name: bad arguments");
+    ORV_REQUIRE(entry != 3 || (attn_fused(scale) && score_bound > 0.f && score_bound <= ORV_STATIC_LIMIT_PP),
+                "orv_attention_kernel_name: the packed entry point needs the fused scale and 0 < score_bound <= %g", (double)ORV_STATIC_LIMIT_PP);
+    const AttnPick pk = attn_pick(entries[entry], entry == 1, attn_fused(scale), aligned_out != 0, score_bound, {}, attn_switches(), attn_items(B, S, H));
+    snprintf(buf, len, "%s", ATTN_FORMS[pk.form].name);
+    return ORV_OK;
 }

@@ -1143,10 +1143,9 @@ extern "C" int orv_attention_bwd(const void* qkv, int ld_qkv, const void* qT, co
                                  void* stream) {
     ORV_REQUIRE(qkv && out && dout && lse && neg_lse2 && neg_delta && dqkv, "orv_attention_bwd: null operand");
     ORV_REQUIRE(s_pad == ((S + 63) / 64) * 64, "orv_attention_bwd: s_pad must be S rounded up to 64");
-    static int use_pp = -1;
-    if (use_pp < 0) { const char* e = getenv("ORV_ATTN_BWD_PP"); use_pp = (e && atoi(e) == 0) ? 0 : 1; }
+    static const bool use_pp = orv_env_int("ORV_ATTN_BWD_PP", 1) != 0;
     const bool have_t = qT && kT && doT;
-    const bool pp = (use_pp || !have_t) && ld_dqkv % 8 == 0 && ((uintptr_t)dqkv & 15) == 0;
+    const bool pp = (use_pp || !have_t) && ld_dqkv % 8 == 0 && orv_aligned(dqkv, 16);
     ORV_REQUIRE(pp || have_t, "orv_attention_bwd: the transposed-copy kernels need qT, kT and doT (or a 16-byte aligned dqkv for the ping-pong kernels)");
     hipStream_t st = (hipStream_t)stream;
     const long groups = (long)B * s_pad * H;
@@ -1165,8 +1164,7 @@ extern "C" int orv_attention_bwd(const void* qkv, int ld_qkv, const void* qT, co
         // The two passes are independent (dQ | dK, dV: disjoint columns of dqkv) and each is 1560 one-per-CU workgroups = 6.09 -> 7
         // rounds of 256 CUs at B = 4: launched on two streams the dispatcher fills the empty part of one pass's last round with
         // the other's workgroups (fork / join by events, legal under stream capture).  ORV_ATTN_BWD_FORK=0: back to back.
-        static int fork = -1;
-        if (fork < 0) { const char* e = getenv("ORV_ATTN_BWD_FORK"); fork = (e && atoi(e) == 0) ? 0 : 1; }
+        static const bool fork = orv_env_int("ORV_ATTN_BWD_FORK", 1) != 0;
         std::lock_guard<std::mutex> lock(g_bwd_side_mutex);
         BwdSide* side = fork ? bwd_side() : nullptr;
         // a failed fork (event record / wait refused) must not let the dK / dV pass run unordered against its inputs: fall back to

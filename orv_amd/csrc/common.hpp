@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 #include <stdarg.h>
 #include "../../include/orv_mi355.h"
 
@@ -22,6 +24,18 @@ int orv_check_launch(const char* what);
             return ORV_EINVAL;                 \
         }                                      \
     } while (0)
+
+// Host helpers of the launch functions.
+// A process switch (ORV_*): the variable's integer value, `dflt` when it is unset.  Callers keep the result in a `static const`, so a
+// switch is read once per process.  On/off switches test `!= 0`: dflt 1 = off only when the variable parses to 0, dflt 0 = opt-in.
+// field > 0: that comma-separated field of a list switch ("ring,bm,bn"), `dflt` when the list is shorter.
+inline int orv_env_int(const char* name, int dflt, int field = 0) {
+    const char* e = getenv(name);
+    for (; e && field > 0; --field) { e = strchr(e, ','); if (e) ++e; }
+    return e ? atoi(e) : dflt;
+}
+inline bool orv_aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }   // n: a power of two
+inline unsigned orv_blocks(long n, int per) { return (unsigned)((n + per - 1) / per); }         // 1-D grid: ceil(n / per)
 
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // round-to-nearest-even fp32 -> bf16 (NaN kept quiet)

@@ -1035,6 +1035,12 @@ struct GemmCand { int ring, bm, bn; float rate; int min_rounds; };
 #endif
 #define T8R192_RATE_256 ORV_T8R192_RATE_256
 #define T8R192_RATE_192 ORV_T8R192_RATE_192
+// ORV_GEMM_WALK_BACK: tiles handed out from the END of the list (GemmArgs::walk_back): 0 never, 1 the gated-residual GEMMs only
+// (out-projection, FFN2), 2 (default) every GEMM
+static int gemm_walk_back_mode() {
+    static const int wb = orv_env_int("ORV_GEMM_WALK_BACK", 2);
+    return wb;
+}
 // C[M, N] (+)= A[K, M]^T . W[K, N]: the TN form of gemm_t8.hip (weight gradients: A = dY [tokens, out], W = X [tokens, in]; reference:
 // torch autograd of nn.Linear inside accelerator.backward, train_cogvideox_control_to_video_sft.py:1093).  bf16 in, fp32 accumulate, bf16 out;
 // accumulate != 0: C += the product (gradient accumulation).  N % 192 == 0 or N % 256 == 0, M % 8 == 0; any K (rows past K are zeros).
@@ -1060,7 +1066,7 @@ extern "C" int orv_gemm_tn_bf16(const void* A, long lda, const void* W, long ldw
     const int bn = waste(256) <= waste(192) ? 256 : 192;
     a.tiles_n = N / bn;
     a.tiles_m = (M + 255) / 256;
-    { static int wb = -1; if (wb < 0) { const char* e = getenv("ORV_GEMM_WALK_BACK"); wb = e ? atoi(e) : 2; } a.walk_back = wb == 2 ? 1 : 0; }
+    a.walk_back = gemm_walk_back_mode() == 2 ? 1 : 0;
     return launch_t8_tn(a, bn, accumulate ? 1 : 0, (hipStream_t)stream);
 }
 
@@ -1106,32 +1112,26 @@ static const GemmCand* choose_tile(int M, int N, int K, int epilogue = 0, int he
         // 192 rows (2 x 4 wave grid): M = 3226 (one clip) is 17 tiles, 17 x 15 = 255 tiles for N = 1920
         {0, 192, 128, 0.920f, 0},
     };
-    if (g_force_ring < 0) {
-        g_force_ring = 2;
-        if (const char* e = getenv("ORV_GEMM_TILE")) sscanf(e, "%d,%d,%d", &g_force_ring, &g_force_bm, &g_force_bn);
-        if (const char* e = getenv("ORV_GEMM_ALGO")) { if (atoi(e) == 0) g_force_ring = 0; }   // legacy switch: simple kernel only
+    if (g_force_ring < 0) {      // no orv_gemm_force_tile call yet: the pin of the environment, read once (fields left out keep 2 / 0 / 0)
+        g_force_ring = orv_env_int("ORV_GEMM_TILE", 2, 0);
+        g_force_bm = orv_env_int("ORV_GEMM_TILE", 0, 1);
+        g_force_bn = orv_env_int("ORV_GEMM_TILE", 0, 2);
+        if (orv_env_int("ORV_GEMM_ALGO", 1) == 0) g_force_ring = 0;   // legacy switch: simple kernel only
     }
     const int force_ring = g_force_ring, force_bm = g_force_bm, force_bn = g_force_bn;
-    static int no_phased = -1;   // ORV_GEMM_PHASED=0: A/B switch for the phased kernel
-    if (no_phased < 0) { const char* e = getenv("ORV_GEMM_PHASED"); no_phased = (e && atoi(e) == 0) ? 1 : 0; }
-    static int no_t8 = -1;       // ORV_GEMM_T8=0: A/B switch for the t8 kernel
-    if (no_t8 < 0) { const char* e = getenv("ORV_GEMM_T8"); no_t8 = (e && atoi(e) == 0) ? 1 : 0; }
-    static int no_r192 = -1;     // ORV_GEMM_R192=0: A/B switch for the 192-row t8 tiles
-    if (no_r192 < 0) { const char* e = getenv("ORV_GEMM_R192"); no_r192 = (e && atoi(e) == 0) ? 1 : 0; }
-    static int no_d8 = -1;       // ORV_GEMM_D8=0: A/B switch for the d8 kernel
-    if (no_d8 < 0) { const char* e = getenv("ORV_GEMM_D8"); no_d8 = (e && atoi(e) == 0) ? 1 : 0; }
-    static int no_d8r192 = -1;   // ORV_GEMM_D8R192=0: A/B switch for the 192-row d8 tiles
-    if (no_d8r192 < 0) { const char* e = getenv("ORV_GEMM_D8R192"); no_d8r192 = (e && atoi(e) == 0) ? 1 : 0; }
-    static int no384 = -1;   // ORV_GEMM_BN384=0: A/B switch for the 384-wide variant
-    if (no384 < 0) { const char* e = getenv("ORV_GEMM_BN384"); no384 = (e && atoi(e) == 0) ? 1 : 0; }
+    // A/B switches, all on unless set to 0: the phased kernel, the t8 kernel and its 192-row tiles, the d8 kernel and its 192-row tiles,
+    // the 384-wide variant
+    struct Off { bool phased, t8, r192, d8, d8r192, bn384; };
+    static const Off off = {orv_env_int("ORV_GEMM_PHASED", 1) == 0, orv_env_int("ORV_GEMM_T8", 1) == 0,     orv_env_int("ORV_GEMM_R192", 1) == 0,
+                            orv_env_int("ORV_GEMM_D8", 1) == 0,     orv_env_int("ORV_GEMM_D8R192", 1) == 0, orv_env_int("ORV_GEMM_BN384", 1) == 0};
     const int ncu = orv_num_cus();
     const GemmCand* best = nullptr;
     double best_cost = 0;
     for (const GemmCand& c : cands) {
         if (N % c.bn) continue;
-        if (c.ring == 2 && (K % 128 != 0 || no_phased)) continue;
-        if (c.ring == 3 && (K % 128 != 0 || no_t8 || wide || (epilogue == 4 && c.bn != 256))) continue;
-        if (c.ring == 3 && c.bm == 192 && (no_r192 || epilogue == 3)) continue;
+        if (c.ring == 2 && (K % 128 != 0 || off.phased)) continue;
+        if (c.ring == 3 && (K % 128 != 0 || off.t8 || wide || (epilogue == 4 && c.bn != 256))) continue;
+        if (c.ring == 3 && c.bm == 192 && (off.r192 || epilogue == 3)) continue;
         // packed C has orv_packed_rows(M) = ceil(M / 256) * 256 row slots and the packed store is not masked: the 192-row tiling must fit them
         if (c.ring == 3 && c.bm == 192 && cpacked && (long)((M + 191) / 192) * 192 > (long)((M + 255) / 256) * 256) continue;
         if (c.ring == 4 && (K % 128 != 0 || wide || epilogue > 2 || force_ring != 4)) continue;
@@ -1139,9 +1139,9 @@ static const GemmCand* choose_tile(int M, int N, int K, int epilogue = 0, int he
         if ((c.ring == 5) != packed) continue;
         // packed C from row-major A: only the t8 kernel's 256-wide GELU epilogue writes it
         if (cpacked && !packed && !(c.ring == 3 && c.bn == 256 && epilogue == 1)) continue;
-        if (c.ring == 5 && (K % 192 != 0 || no_d8)) continue;
+        if (c.ring == 5 && (K % 192 != 0 || off.d8)) continue;
         // 192-row d8 tiles: the packed A (and C) buffers hold ceil(M / 256) * 256 row slots and neither A loads nor the packed store are masked
-        if (c.ring == 5 && c.bm == 192 && (no_d8r192 || epilogue == 3 || (long)((M + 191) / 192) * 192 > (long)((M + 255) / 256) * 256)) continue;
+        if (c.ring == 5 && c.bm == 192 && (off.d8r192 || epilogue == 3 || (long)((M + 191) / 192) * 192 > (long)((M + 255) / 256) * 256)) continue;
         // epilogue 4 normalises whole 64-wide heads inside a wave (BN / 2 columns) that must not straddle q | k | v
         if (epilogue == 4 && c.ring != 5 && ((c.bm == 192 && c.ring != 3) || (c.bn / 2) % 64 != 0 || (heads * 64) % (c.bn / 2) != 0)) continue;
         if (force_bm && (c.ring != force_ring || c.bm != force_bm || c.bn != force_bn)) continue;
@@ -1151,7 +1151,7 @@ static const GemmCand* choose_tile(int M, int N, int K, int epilogue = 0, int he
         // sweep: FFN2, N = 1920 = 5 x 384, K = 7680 is 255 tiles of 120 K-tiles: 0.391 vs 0.403 ms on 256 x 192)
         const bool one_long_round = K >= 4096 && tiles <= ncu && tiles * 20 >= (long)ncu * 19;
         if (!force_bm && tiles < (long)c.min_rounds * ncu && !one_long_round) continue;
-        if (!force_bm && c.ring == 1 && c.bn == 384 && no384) continue;
+        if (!force_bm && c.ring == 1 && c.bn == 384 && off.bn384) continue;
         // full rounds cost 1 each; the last, partial round runs faster than a full one because the chip is power-capped
         // (fewer active CUs clock higher): 0.62 (= 1.5 GHz / 2.4 GHz) + 0.38 x the fraction of CUs it occupies.
         // Rows of the last M tile that do not exist still cost their MFMAs (tiles are counted whole).
@@ -1170,8 +1170,7 @@ static const GemmCand* choose_tile(int M, int N, int K, int epilogue = 0, int he
 // operand is read by both launches (L2 / Infinity Cache).  ORV_GEMM_QKV_SPLIT=0: A/B switch.
 static bool plan_gemm(int M, int N, int K, int epilogue, int heads, const GemmCand*& first, const GemmCand*& second, bool wide = false,
                       bool packed = false, bool cpacked = false) {
-    static int qkv_split = -1;
-    if (qkv_split < 0) { const char* e = getenv("ORV_GEMM_QKV_SPLIT"); qkv_split = (e && atoi(e) == 0) ? 0 : 1; }
+    static const bool qkv_split = orv_env_int("ORV_GEMM_QKV_SPLIT", 1) != 0;
     second = nullptr;
     first = choose_tile(M, N, K, epilogue, heads, wide, packed, cpacked);
     if (packed || cpacked) return first != nullptr;      // the d8 kernel normalises 64-column groups at any BN: no q | k + v split
@@ -1220,11 +1219,8 @@ extern "C" int orv_gemm_kernel_name_packed(int M, int N, int K, int epilogue, in
 static int gemm_dispatch(GemmArgs a, const GemmCand* best, int epilogue, hipStream_t st) {
     a.tiles_n = a.N / best->bn;
     a.tiles_m = (a.M + best->bm - 1) / best->bm;
-    {
-        static int gm_env = -1;
-        if (gm_env < 0) { const char* e = getenv("ORV_GEMM_GM"); gm_env = e ? atoi(e) : 0; }
-        a.gm = gm_env > 0 ? gm_env : (a.K >= 4096 && a.tiles_n <= 16 ? 8 : 0);
-    }
+    static const int gm_env = orv_env_int("ORV_GEMM_GM", 0);
+    a.gm = gm_env > 0 ? gm_env : (a.K >= 4096 && a.tiles_n <= 16 ? 8 : 0);
     if (best->ring == 3) return launch_t8(a, best->bn, epilogue, st, best->bm);
     if (best->ring == 4) return launch_t4(a, epilogue, st);
     if (best->ring == 5) return launch_d8(a, best->bn, epilogue, st, best->bm);
@@ -1280,22 +1276,14 @@ extern "C" int orv_gemm_bf16(const orv_gemm_t* g, void* stream) {
                     "orv_gemm_bf16: epilogue 4 needs N = 3 * heads * 64 (q | k | v) or 2 * heads * 64 (q | k) (N=%d heads=%d)", g->N, g->qn_heads);
         ORV_REQUIRE(g->cmap.rows == 0, "orv_gemm_bf16: epilogue 4 writes rows in place (no cmap)");
     }
-    { static int dbg = -1; if (dbg < 0) { const char* e = getenv("ORV_GEMM_DBG"); dbg = e ? atoi(e) : 0; } a.dbg = dbg; }
-    {   // ORV_T8_STAGGER="groups,ns": start stagger of the t8 workgroups; ORV_T8_GRID: cap of persistent workgroups (experiments)
-        static int sg = -1, st_ticks = 0, gcap = 0;
-        if (sg < 0) {
-            sg = 0;
-            if (const char* e = getenv("ORV_T8_STAGGER")) { int ns = 0; if (sscanf(e, "%d,%d", &sg, &ns) == 2) st_ticks = ns / 10; else sg = 0; }
-            if (const char* e = getenv("ORV_T8_GRID")) gcap = atoi(e);
-        }
-        a.stagger_groups = sg; a.stagger_ticks = st_ticks; a.grid_cap = gcap;
+    { static const int dbg = orv_env_int("ORV_GEMM_DBG", 0); a.dbg = dbg; }
+    {   // ORV_T8_STAGGER="groups,ns": start stagger of the t8 workgroups (both fields, else none); ORV_T8_GRID: cap of persistent
+        // workgroups (experiments)
+        static const int ns = orv_env_int("ORV_T8_STAGGER", -1, 1), sg = ns < 0 ? 0 : orv_env_int("ORV_T8_STAGGER", 0);
+        static const int gcap = orv_env_int("ORV_T8_GRID", 0);
+        a.stagger_groups = sg; a.stagger_ticks = ns < 0 ? 0 : ns / 10; a.grid_cap = gcap;
     }
-    {   // tiles handed out from the END of the list (GemmArgs::walk_back).  ORV_GEMM_WALK_BACK: 0 never, 1 the gated-residual GEMMs
-        // only (out-projection, FFN2), 2 (default) every GEMM
-        static int wb = -1;
-        if (wb < 0) { const char* e = getenv("ORV_GEMM_WALK_BACK"); wb = e ? atoi(e) : 2; }
-        a.walk_back = (wb == 2 || (wb == 1 && g->epilogue == 2 && g->gate)) ? 1 : 0;
-    }
+    { const int wb = gemm_walk_back_mode(); a.walk_back = (wb == 2 || (wb == 1 && g->epilogue == 2 && g->gate)) ? 1 : 0; }
     hipStream_t st = (hipStream_t)stream;
     const GemmCand *first = nullptr, *second = nullptr;
     const bool wide = (long)g->M * g->lda * 2 >= (1L << 32) || (long)g->N * g->ldw * 2 >= (1L << 32);
@@ -1336,14 +1324,11 @@ extern "C" int orv_conv_gemm_bf16(const orv_gemm_t* g, const orv_conv_t* c, void
     ConvArgs cv{(const bf16_t*)c->src, c->B, c->Ts, c->Hs, c->Ws, c->C, c->T, c->H, c->W, c->kt, c->kh, c->kw, c->stride, c->pad_lo,
                 c->ups_s, c->ups_t, c->t_shift};
     hipStream_t st0 = (hipStream_t)stream;
-    static int use_strip = -1;       // ORV_CONV_STRIP=0: A/B switch
-    if (use_strip < 0) { const char* e = getenv("ORV_CONV_STRIP"); use_strip = (e && atoi(e) == 0) ? 0 : 1; }
+    static const bool use_strip = orv_env_int("ORV_CONV_STRIP", 1) != 0;         // ORV_CONV_STRIP=0: A/B switch
     if (use_strip && c->stride == 1 && !c->ups_s && !c->ups_t && c->Hs == c->H && c->Ws == c->W && c->kw == 3 && c->pad_lo == 1 &&
         c->W >= 2 && g->N % 128 == 0 && g->r_mod == 0) {
-        static int bm384 = -1;       // ORV_CONV_BM384=0: A/B switch for the 384-row tile of the 128-wide convolutions
-        if (bm384 < 0) { const char* e = getenv("ORV_CONV_BM384"); bm384 = (e && atoi(e) == 0) ? 0 : 1; }
-        static int small = -1;       // ORV_CONV_SMALL=0: A/B switch for the small-grid tiles
-        if (small < 0) { const char* e = getenv("ORV_CONV_SMALL"); small = (e && atoi(e) == 0) ? 0 : 1; }
+        static const bool bm384 = orv_env_int("ORV_CONV_BM384", 1) != 0;         // =0: A/B switch for the 384-row tile of the 128-wide convolutions
+        static const bool small = orv_env_int("ORV_CONV_SMALL", 1) != 0;         // =0: A/B switch for the small-grid tiles
         // tile: 256 x 256 where it fills the chip; the low-resolution stages of the decoder (7200 voxels x 512 channels: 58 tiles
         // of 256 x 256 on 256 CUs) take 256 x 128, then 128 x 128 tiles while the grid covers less than half of the CUs
         const int ncu = orv_num_cus();

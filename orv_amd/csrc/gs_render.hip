@@ -251,7 +251,6 @@ __global__ __launch_bounds__(256) void gs_render_kernel(const GsRenderArgs a) {
     }
 }
 
-inline bool gs_aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 inline long gs_tiles(int H, int W) { return (long)((H + GS_TILE - 1) / GS_TILE) * ((W + GS_TILE - 1) / GS_TILE); }
 
 }  // namespace
@@ -267,7 +266,7 @@ extern "C" int orv_gs_preprocess(const float* means3D, const float* scales, cons
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(means3D && scales && rotations && opacities, "orv_gs_preprocess: null pointer (means3D / scales / rotations / opacities)");
     ORV_REQUIRE(xy && conic_opacity && depth && radii && rect && tiles_touched, "orv_gs_preprocess: null pointer (an output buffer)");
-    ORV_REQUIRE(gs_aligned(conic_opacity, 16) && gs_aligned(rect, 16), "orv_gs_preprocess: conic_opacity and rect must be 16-byte aligned");
+    ORV_REQUIRE(orv_aligned(conic_opacity, 16) && orv_aligned(rect, 16), "orv_gs_preprocess: conic_opacity and rect must be 16-byte aligned");
     ORV_REQUIRE(gs_tiles(H, W) < (1L << 31), "orv_gs_preprocess: %d x %d has 2^31 tiles or more", H, W);
     GsPreArgs a;
     a.means = means3D, a.scales = scales, a.rots = rotations, a.opac = opacities, a.view = viewmatrix, a.proj = projmatrix;
@@ -285,7 +284,7 @@ extern "C" int orv_gs_tile_keys(const int* rect, const float* depth, const long*
     ORV_REQUIRE(gs_tiles(H, W) < (1L << 31), "orv_gs_tile_keys: %d x %d has 2^31 tiles or more", H, W);
     if (N == 0 || L == 0) return ORV_OK;
     ORV_REQUIRE(rect && depth && offsets && keys && gaussian_idx, "orv_gs_tile_keys: null pointer");
-    ORV_REQUIRE(gs_aligned(rect, 16) && gs_aligned(offsets, 8) && gs_aligned(keys, 8), "orv_gs_tile_keys: rect must be 16-byte, offsets and keys 8-byte aligned");
+    ORV_REQUIRE(orv_aligned(rect, 16) && orv_aligned(offsets, 8) && orv_aligned(keys, 8), "orv_gs_tile_keys: rect must be 16-byte, offsets and keys 8-byte aligned");
     hipLaunchKernelGGL(gs_tile_keys_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rect, depth, offsets, N,
                        (W + GS_TILE - 1) / GS_TILE, L, keys, gaussian_idx);
     return orv_check_launch("orv_gs_tile_keys");
@@ -298,7 +297,7 @@ extern "C" int orv_gs_tile_ranges(const long* sorted_keys, long L, int H, int W,
     ORV_REQUIRE(ranges, "orv_gs_tile_ranges: null pointer (ranges)");
     if (L == 0) return ORV_OK;
     ORV_REQUIRE(sorted_keys, "orv_gs_tile_ranges: null pointer (sorted_keys)");
-    ORV_REQUIRE(gs_aligned(sorted_keys, 8), "orv_gs_tile_ranges: sorted_keys must be 8-byte aligned");
+    ORV_REQUIRE(orv_aligned(sorted_keys, 8), "orv_gs_tile_ranges: sorted_keys must be 8-byte aligned");
     hipLaunchKernelGGL(gs_tile_ranges_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sorted_keys, L,
                        (int)gs_tiles(H, W), ranges);
     return orv_check_launch("orv_gs_tile_ranges");
@@ -315,7 +314,7 @@ extern "C" int orv_gs_render(const int* ranges, const int* point_list, long L, c
     ORV_REQUIRE(ranges && bg && out_color && out_depth && out_alpha && (F == 0 || out_feature), "orv_gs_render: null pointer (ranges / bg / an output plane)");
     ORV_REQUIRE(L == 0 || (N > 0 && point_list && xy && conic_opacity && depth && colors && (F == 0 || features)),
                 "orv_gs_render: null pointer (a per-Gaussian array) with L = %ld pairs", L);
-    ORV_REQUIRE(gs_aligned(conic_opacity, 16), "orv_gs_render: conic_opacity must be 16-byte aligned");
+    ORV_REQUIRE(orv_aligned(conic_opacity, 16), "orv_gs_render: conic_opacity must be 16-byte aligned");
     GsRenderArgs a;
     a.ranges = ranges, a.list = point_list, a.xy = xy, a.conic_op = conic_opacity, a.depth = depth, a.colors = colors, a.feats = features;
     a.bg = bg, a.out_color = out_color, a.out_feat = out_feature, a.out_depth = out_depth, a.out_alpha = out_alpha;

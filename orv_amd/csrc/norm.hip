@@ -375,8 +375,7 @@ static int layernorm_modulate_impl(const void* x, int ldx, orv_rowmap_t xmap, vo
     ORV_REQUIRE(!mx || (!packed && D % 32 == 0), "orv_layernorm_modulate_mxfp8: D=%d must be a multiple of 32", D);
     // rows-per-wave form: big FULL launches without a row map; R = rows per wave so that one round of resident waves (12 per CU) covers
     // the problem.  ORV_LN_ROWS=0: the one-row kernel everywhere (A/B); ORV_LN_ROWS=n: fixed R.
-    static int rows_env = -2;
-    if (rows_env == -2) { const char* e = getenv("ORV_LN_ROWS"); rows_env = e ? atoi(e) : -1; }
+    static const int rows_env = orv_env_int("ORV_LN_ROWS", -1);
     ORV_REQUIRE(!packed || (full && xmap.rows == 0 && ch <= 4 && D % 32 == 0 && ldy == D),
                 "orv_layernorm_modulate_packed: needs gamma, beta, scale, shift, no row map, D %% 32 == 0, D <= 2048 and ldy == D");
     // Every full, map-free launch with D <= 2048 takes the rows kernel, whatever the row count (below 2048 rows the one-row kernel
@@ -703,8 +702,7 @@ extern "C" int orv_modulation_tables(const void* temb, const void* action_emb, c
     const int nblocks = width / 32;
     dim3 grid(max(1, min((nblocks + 11) / 12, 64)), n_tab, a.vis_tiles + txt_tiles);
     hipStream_t st = (hipStream_t)stream;
-    static int lds_env = -1;     // ORV_MOD_TABLES_LDS=0: the direct-load kernel for E = 512 too (A/B)
-    if (lds_env < 0) { const char* e = getenv("ORV_MOD_TABLES_LDS"); lds_env = (e && atoi(e) == 0) ? 0 : 1; }
+    static const bool lds_env = orv_env_int("ORV_MOD_TABLES_LDS", 1) != 0;       // =0: the direct-load kernel for E = 512 too (A/B)
     if (E == 512 && lds_env) {
         dim3 g2((nblocks + 4 * MT_MAXBLK - 1) / (4 * MT_MAXBLK), n_tab, a.vis_tiles + txt_tiles);
         hipLaunchKernelGGL(mod_tables_lds_kernel, g2, dim3(256), 0, st, a);

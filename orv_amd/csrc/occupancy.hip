@@ -114,9 +114,6 @@ __global__ __launch_bounds__(256) void oc_write_kernel(const OcWriteArgs a) {
     for (int c = 0; c < a.F; ++c) f[c] = c == rank ? 1.0f : 0.0f;
 }
 
-inline bool oc_aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-inline unsigned oc_blocks(int n) { return (unsigned)(((long)n + 255) / 256); }
-
 }  // namespace
 
 extern "C" int orv_occ_project_labels(const float* points, int N, int C, const float* P, const void* labels2d, int label_bytes, int H, int W,
@@ -127,13 +124,13 @@ extern "C" int orv_occ_project_labels(const float* points, int N, int C, const f
     ORV_REQUIRE(label_bytes == 1 || label_bytes == 4, "orv_occ_project_labels: label_bytes = %d; supported: 1 (uint8) or 4 (int32)", label_bytes);
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(points && P && labels2d && labels3d, "orv_occ_project_labels: null pointer (points / P / labels2d / labels3d)");
-    ORV_REQUIRE(oc_aligned(points, 4) && oc_aligned(P, 4) && oc_aligned(labels2d, (uintptr_t)label_bytes) && oc_aligned(labels3d, 8),
+    ORV_REQUIRE(orv_aligned(points, 4) && orv_aligned(P, 4) && orv_aligned(labels2d, (uintptr_t)label_bytes) && orv_aligned(labels3d, 8),
                 "orv_occ_project_labels: points and P must be 4-byte, labels2d element and labels3d 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (label_bytes == 1)
-        hipLaunchKernelGGL(oc_project_kernel<unsigned char>, dim3(oc_blocks(N)), dim3(256), 0, s, points, N, C, P, (const unsigned char*)labels2d, H, W, labels3d);
+        hipLaunchKernelGGL(oc_project_kernel<unsigned char>, dim3(orv_blocks(N, 256)), dim3(256), 0, s, points, N, C, P, (const unsigned char*)labels2d, H, W, labels3d);
     else
-        hipLaunchKernelGGL(oc_project_kernel<int>, dim3(oc_blocks(N)), dim3(256), 0, s, points, N, C, P, (const int*)labels2d, H, W, labels3d);
+        hipLaunchKernelGGL(oc_project_kernel<int>, dim3(orv_blocks(N, 256)), dim3(256), 0, s, points, N, C, P, (const int*)labels2d, H, W, labels3d);
     return orv_check_launch("orv_occ_project_labels");
 }
 
@@ -148,8 +145,8 @@ extern "C" int orv_occ_cell_keys(const int* occ, int M, int X, int Y, int Z, lon
     if (int e = oc_check_grid("orv_occ_cell_keys", X, Y, Z)) return e;
     if (M == 0) return ORV_OK;
     ORV_REQUIRE(occ && keys && state, "orv_occ_cell_keys: null pointer (occ / keys / state)");
-    ORV_REQUIRE(oc_aligned(occ, 16) && oc_aligned(keys, 8) && oc_aligned(state, 8), "orv_occ_cell_keys: occ must be 16-byte, keys and state 8-byte aligned");
-    hipLaunchKernelGGL(oc_keys_kernel, dim3(oc_blocks(M)), dim3(256), 0, (hipStream_t)stream, occ, M, X, Y, Z, keys, state);
+    ORV_REQUIRE(orv_aligned(occ, 16) && orv_aligned(keys, 8) && orv_aligned(state, 8), "orv_occ_cell_keys: occ must be 16-byte, keys and state 8-byte aligned");
+    hipLaunchKernelGGL(oc_keys_kernel, dim3(orv_blocks(M, 256)), dim3(256), 0, (hipStream_t)stream, occ, M, X, Y, Z, keys, state);
     return orv_check_launch("orv_occ_cell_keys");
 }
 
@@ -157,9 +154,9 @@ extern "C" int orv_occ_mark_cells(const long* sorted_keys, const long* order, co
     ORV_REQUIRE(M >= 0, "orv_occ_mark_cells: M must not be negative (got %d)", M);
     if (M == 0) return ORV_OK;
     ORV_REQUIRE(sorted_keys && order && occ && last && state, "orv_occ_mark_cells: null pointer");
-    ORV_REQUIRE(oc_aligned(sorted_keys, 8) && oc_aligned(order, 8) && oc_aligned(state, 8) && oc_aligned(occ, 4) && oc_aligned(last, 4),
+    ORV_REQUIRE(orv_aligned(sorted_keys, 8) && orv_aligned(order, 8) && orv_aligned(state, 8) && orv_aligned(occ, 4) && orv_aligned(last, 4),
                 "orv_occ_mark_cells: sorted_keys, order and state must be 8-byte, occ and last 4-byte aligned");
-    hipLaunchKernelGGL(oc_mark_kernel, dim3(oc_blocks(M)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order, occ, M, last, state);
+    hipLaunchKernelGGL(oc_mark_kernel, dim3(orv_blocks(M, 256)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order, occ, M, last, state);
     return orv_check_launch("orv_occ_mark_cells");
 }
 
@@ -179,13 +176,13 @@ extern "C" int orv_occ_write_gaussians(const long* order, const int* occ, const 
     ORV_REQUIRE(order && occ && last && csum, "orv_occ_write_gaussians: null pointer (an input array)");
     ORV_REQUIRE(ax && ay && az && zscale, "orv_occ_write_gaussians: null pointer (a table)");
     ORV_REQUIRE(xyz && rgb && feat && rot && scale && opacity, "orv_occ_write_gaussians: null pointer (an output buffer)");
-    ORV_REQUIRE(oc_aligned(order, 8) && oc_aligned(occ, 16) && oc_aligned(rot, 16),
+    ORV_REQUIRE(orv_aligned(order, 8) && orv_aligned(occ, 16) && orv_aligned(rot, 16),
                 "orv_occ_write_gaussians: order must be 8-byte, occ and rot 16-byte aligned");
     OcWriteArgs a;
     a.order = order, a.occ = occ, a.last = last, a.csum = csum;
     a.ax = ax, a.ay = ay, a.az = az, a.zscale = zscale;
     a.xyz = xyz, a.rgb = rgb, a.feat = feat, a.rot = rot, a.scale = scale, a.opacity = opacity;
     a.classes = classes, a.M = M, a.n = n, a.X = X, a.Y = Y, a.Z = Z, a.F = F;
-    hipLaunchKernelGGL(oc_write_kernel, dim3(oc_blocks(M)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(oc_write_kernel, dim3(orv_blocks(M, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return orv_check_launch("orv_occ_write_gaussians");
 }

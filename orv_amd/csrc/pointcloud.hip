@@ -395,9 +395,6 @@ __global__ __launch_bounds__(256) void pc_orient_kernel(const float* __restrict_
     out[3 * (long)i] = (float)nx, out[3 * (long)i + 1] = (float)ny, out[3 * (long)i + 2] = (float)nz;
 }
 
-inline bool pc_aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-inline unsigned pc_blocks(long n, int per) { return (unsigned)((n + per - 1) / per); }
-
 // the grid of an entry point, or false with the error set
 bool pc_grid(const char* who, float x0, float y0, float z0, double cell, int gx, int gy, int gz, PcGrid* gr) {
     if (!(cell > 0.0 && cell < 1e300)) {
@@ -429,8 +426,8 @@ extern "C" int orv_pc_cells(const float* points, int N, float x0, float y0, floa
     if (!pc_grid(who, x0, y0, z0, cell, gx, gy, gz, &gr)) return ORV_EINVAL;
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(points && keys, "%s: null pointer (points / keys)", who);
-    ORV_REQUIRE(pc_aligned(points, 4) && pc_aligned(keys, 8), "%s: points must be 4-byte and keys 8-byte aligned", who);
-    hipLaunchKernelGGL(pc_cells_kernel, dim3(pc_blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, points, N, gr, keys);
+    ORV_REQUIRE(orv_aligned(points, 4) && orv_aligned(keys, 8), "%s: points must be 4-byte and keys 8-byte aligned", who);
+    hipLaunchKernelGGL(pc_cells_kernel, dim3(orv_blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, points, N, gr, keys);
     return orv_check_launch(who);
 }
 
@@ -441,10 +438,10 @@ extern "C" int orv_pc_cell_table(const long* sorted_keys, const long* order, con
     ORV_REQUIRE(n_cells >= 1 && n_cells <= PC_MAX_CELLS, "%s: n_cells = %d; supported: 1 to %ld", who, n_cells, PC_MAX_CELLS);
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(sorted_keys && order && points && start && sorted_points, "%s: null pointer", who);
-    ORV_REQUIRE(pc_aligned(sorted_keys, 8) && pc_aligned(order, 8) && pc_aligned(points, 4) && pc_aligned(start, 4) && pc_aligned(sorted_points, 4),
+    ORV_REQUIRE(orv_aligned(sorted_keys, 8) && orv_aligned(order, 8) && orv_aligned(points, 4) && orv_aligned(start, 4) && orv_aligned(sorted_points, 4),
                 "%s: sorted_keys and order must be 8-byte, points, start and sorted_points 4-byte aligned", who);
     const long threads = N > n_cells + 1 ? N : n_cells + 1;
-    hipLaunchKernelGGL(pc_cell_table_kernel, dim3(pc_blocks(threads, 256)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order, points, N, n_cells,
+    hipLaunchKernelGGL(pc_cell_table_kernel, dim3(orv_blocks(threads, 256)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order, points, N, n_cells,
                        start, sorted_points);
     return orv_check_launch(who);
 }
@@ -459,11 +456,11 @@ extern "C" int orv_pc_knn(const float* sorted_points, const long* order, const i
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(sorted_points && order && start, "%s: null pointer (sorted_points / order / start)", who);
     ORV_REQUIRE(idx && d2 && pending, "%s: null pointer (idx / d2 / pending)", who);
-    ORV_REQUIRE(pc_aligned(order, 8) && pc_aligned(d2, 8) && pc_aligned(sorted_points, 4) && pc_aligned(start, 4) && pc_aligned(idx, 4),
+    ORV_REQUIRE(orv_aligned(order, 8) && orv_aligned(d2, 8) && orv_aligned(sorted_points, 4) && orv_aligned(start, 4) && orv_aligned(idx, 4),
                 "%s: order and d2 must be 8-byte, sorted_points, start and idx 4-byte aligned", who);
     a.sorted_points = sorted_points, a.order = order, a.start = start, a.idx = idx, a.d2 = d2, a.pending = pending;
     a.N = N, a.kk = k < N ? k : N;
-    hipLaunchKernelGGL(pc_knn_kernel, dim3(pc_blocks(N, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(pc_knn_kernel, dim3(orv_blocks(N, 4)), dim3(256), 0, (hipStream_t)stream, a);
     return orv_check_launch(who);
 }
 
@@ -474,7 +471,7 @@ extern "C" int orv_pc_knn_brute(const float* points, int N, int k, const long* q
     ORV_REQUIRE(Q >= 0 && Q <= N, "%s: Q = %d queries must be in [0, N = %d]", who, Q, N);
     if (N == 0 || Q == 0) return ORV_OK;
     ORV_REQUIRE(points && queries && idx && d2, "%s: null pointer (points / queries / idx / d2)", who);
-    ORV_REQUIRE(pc_aligned(queries, 8) && pc_aligned(d2, 8) && pc_aligned(points, 4) && pc_aligned(idx, 4),
+    ORV_REQUIRE(orv_aligned(queries, 8) && orv_aligned(d2, 8) && orv_aligned(points, 4) && orv_aligned(idx, 4),
                 "%s: queries and d2 must be 8-byte, points and idx 4-byte aligned", who);
     hipLaunchKernelGGL(pc_knn_brute_kernel, dim3((unsigned)Q), dim3(256), 0, (hipStream_t)stream, points, N, k < N ? k : N, queries, idx, d2);
     return orv_check_launch(who);
@@ -482,7 +479,7 @@ extern "C" int orv_pc_knn_brute(const float* points, int N, int k, const long* q
 
 extern "C" long orv_pc_outlier_workspace(int N) {
     if (N <= 0) return 0;
-    return 2L * (long)pc_blocks(N, PC_CHUNK) * (long)sizeof(double);
+    return 2L * (long)orv_blocks(N, PC_CHUNK) * (long)sizeof(double);
 }
 
 extern "C" int orv_pc_outlier(const double* d2, int N, int k, double std_ratio, double* avg, double* stats, unsigned char* keep,
@@ -494,19 +491,19 @@ extern "C" int orv_pc_outlier(const double* d2, int N, int k, double std_ratio, 
     ORV_REQUIRE(stats, "%s: null pointer (stats)", who);
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(d2 && avg && keep && workspace, "%s: null pointer (d2 / avg / keep / workspace)", who);
-    ORV_REQUIRE(pc_aligned(d2, 8) && pc_aligned(avg, 8) && pc_aligned(stats, 8) && pc_aligned(workspace, 8),
+    ORV_REQUIRE(orv_aligned(d2, 8) && orv_aligned(avg, 8) && orv_aligned(stats, 8) && orv_aligned(workspace, 8),
                 "%s: d2, avg, stats and workspace must be 8-byte aligned", who);
     const long need = orv_pc_outlier_workspace(N);
     ORV_REQUIRE(workspace_bytes >= need, "%s: the workspace holds %ld bytes; orv_pc_outlier_workspace(%d) = %ld", who, workspace_bytes, N, need);
     hipStream_t s = (hipStream_t)stream;
-    const int kk = k < N ? k : N, nb = (int)pc_blocks(N, PC_CHUNK);
+    const int kk = k < N ? k : N, nb = (int)orv_blocks(N, PC_CHUNK);
     double* partials = (double*)workspace;
-    hipLaunchKernelGGL(pc_avg_kernel, dim3(pc_blocks(N, 256)), dim3(256), 0, s, d2, N, kk, avg);
+    hipLaunchKernelGGL(pc_avg_kernel, dim3(orv_blocks(N, 256)), dim3(256), 0, s, d2, N, kk, avg);
     hipLaunchKernelGGL(pc_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const double*)avg, N, (const double*)nullptr, partials);
     hipLaunchKernelGGL(pc_final_kernel, dim3(1), dim3(256), 0, s, (const double*)partials, nb, 0, std_ratio, stats);
     hipLaunchKernelGGL(pc_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const double*)avg, N, (const double*)stats, partials);
     hipLaunchKernelGGL(pc_final_kernel, dim3(1), dim3(256), 0, s, (const double*)partials, nb, 1, std_ratio, stats);
-    hipLaunchKernelGGL(pc_mask_kernel, dim3(pc_blocks(N, 256)), dim3(256), 0, s, (const double*)avg, N, (const double*)stats, keep);
+    hipLaunchKernelGGL(pc_mask_kernel, dim3(orv_blocks(N, 256)), dim3(256), 0, s, (const double*)avg, N, (const double*)stats, keep);
     return orv_check_launch(who);
 }
 
@@ -519,8 +516,8 @@ extern "C" int orv_pc_normals(const float* points, const int* idx, int N, int k,
                 "%s: the camera location must be finite (got %g, %g, %g)", who, camx, camy, camz);
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(points && idx && normals, "%s: null pointer (points / idx / normals)", who);
-    ORV_REQUIRE(pc_aligned(points, 4) && pc_aligned(idx, 4) && pc_aligned(normals, 4), "%s: points, idx and normals must be 4-byte aligned", who);
-    hipLaunchKernelGGL(pc_normals_kernel, dim3(pc_blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, points, idx, N, k < N ? k : N, camx, camy, camz,
+    ORV_REQUIRE(orv_aligned(points, 4) && orv_aligned(idx, 4) && orv_aligned(normals, 4), "%s: points, idx and normals must be 4-byte aligned", who);
+    hipLaunchKernelGGL(pc_normals_kernel, dim3(orv_blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, points, idx, N, k < N ? k : N, camx, camy, camz,
                        normals);
     return orv_check_launch(who);
 }
@@ -532,7 +529,7 @@ extern "C" int orv_pc_orient(const float* points, const float* normals, int N, d
                 "%s: the camera location must be finite (got %g, %g, %g)", who, camx, camy, camz);
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(points && normals && out, "%s: null pointer (points / normals / out)", who);
-    ORV_REQUIRE(pc_aligned(points, 4) && pc_aligned(normals, 4) && pc_aligned(out, 4), "%s: points, normals and out must be 4-byte aligned", who);
-    hipLaunchKernelGGL(pc_orient_kernel, dim3(pc_blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, points, normals, N, camx, camy, camz, out);
+    ORV_REQUIRE(orv_aligned(points, 4) && orv_aligned(normals, 4) && orv_aligned(out, 4), "%s: points, normals and out must be 4-byte aligned", who);
+    hipLaunchKernelGGL(pc_orient_kernel, dim3(orv_blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, points, normals, N, camx, camy, camz, out);
     return orv_check_launch(who);
 }

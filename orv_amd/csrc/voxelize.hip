@@ -175,8 +175,6 @@ __global__ __launch_bounds__(256) void vx_vote_kernel(const VxVoteArgs a) {
     }
 }
 
-inline bool vx_aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 // grid size per axis by the reference's rule, round((hi - lo) / vs) in fp32 (voxelization_cpu.cpp:118-121); false when an axis has no cell
 inline bool vx_grid(const float* vs, const float* range, VxGrid* gr) {
     for (int a = 0; a < 3; ++a) {
@@ -212,7 +210,7 @@ extern "C" int orv_voxel_coors(const float* points, int N, int C, float vx, floa
     ORV_REQUIRE(!keys || (double)gr.g[0] * gr.g[1] * gr.g[2] < 4.0e18, "orv_voxel_coors: %d x %d x %d cells do not fit a 63-bit key", gr.g[0], gr.g[1], gr.g[2]);
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(points && coors, "orv_voxel_coors: null pointer (points / coors)");
-    ORV_REQUIRE(vx_aligned(keys, 8), "orv_voxel_coors: keys must be 8-byte aligned");
+    ORV_REQUIRE(orv_aligned(keys, 8), "orv_voxel_coors: keys must be 8-byte aligned");
     hipLaunchKernelGGL(vx_coors_kernel, dim3((unsigned)(((long)N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, points, N, C, gr, coors, keys);
     return orv_check_launch("orv_voxel_coors");
 }
@@ -221,7 +219,7 @@ extern "C" int orv_voxel_segments(const long* sorted_keys, const long* order, in
     ORV_REQUIRE(N >= 0, "orv_voxel_segments: N must not be negative (got %d)", N);
     if (N == 0) return ORV_OK;
     ORV_REQUIRE(sorted_keys && order && start && seglen && first, "orv_voxel_segments: null pointer");
-    ORV_REQUIRE(vx_aligned(sorted_keys, 8) && vx_aligned(order, 8), "orv_voxel_segments: sorted_keys and order must be 8-byte aligned");
+    ORV_REQUIRE(orv_aligned(sorted_keys, 8) && orv_aligned(order, 8), "orv_voxel_segments: sorted_keys and order must be 8-byte aligned");
     hipLaunchKernelGGL(vx_segments_kernel, dim3((unsigned)(((long)N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order, N, start,
                        seglen, first);
     return orv_check_launch("orv_voxel_segments");
@@ -237,7 +235,7 @@ extern "C" int orv_voxel_scatter(const float* points, const int* point_coors, co
     if (N == 0 || M == 0) return ORV_OK;
     ORV_REQUIRE(points && point_coors && order && start && seglen && csum, "orv_voxel_scatter: null pointer (an input array)");
     ORV_REQUIRE(voxels && coors && num_points_per_voxel, "orv_voxel_scatter: null pointer (an output buffer)");
-    ORV_REQUIRE(vx_aligned(order, 8), "orv_voxel_scatter: order must be 8-byte aligned");
+    ORV_REQUIRE(orv_aligned(order, 8), "orv_voxel_scatter: order must be 8-byte aligned");
     VxScatterArgs a;
     a.points = points, a.pt_coors = point_coors, a.order = order, a.start = start, a.seglen = seglen, a.csum = csum;
     a.voxels = voxels, a.coors = coors, a.num = num_points_per_voxel, a.N = N, a.C = C, a.max_points = max_points, a.M = M;
@@ -254,7 +252,7 @@ extern "C" int orv_voxel_vote(const float* points, const int* point_coors, const
     if (N == 0 || M == 0) return ORV_OK;
     ORV_REQUIRE(points && point_coors && order && start && seglen && csum, "orv_voxel_vote: null pointer (an input array)");
     ORV_REQUIRE(head_of && out, "orv_voxel_vote: null pointer (head_of / out)");
-    ORV_REQUIRE(vx_aligned(order, 8) && vx_aligned(out, 16), "orv_voxel_vote: order must be 8-byte and out 16-byte aligned");
+    ORV_REQUIRE(orv_aligned(order, 8) && orv_aligned(out, 16), "orv_voxel_vote: order must be 8-byte and out 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(vx_heads_kernel, dim3((unsigned)(((long)N + 255) / 256)), dim3(256), 0, s, order, start, csum, N, M, head_of);
     VxVoteArgs a;

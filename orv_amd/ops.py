@@ -321,6 +321,16 @@ def attention_ws_bytes(B, S, H):
     return int(lib().orv_attention_ws_bytes(int(B), int(S), int(H)))
 
 
+def attention_kernel_name(entry, B, S, H, scale, score_bound=0.0, aligned_out=True) -> str:
+    """Kernel symbol(s) a forward-attention entry point launches for this call (``orv_attention_kernel_name``; no GPU work).
+    ``entry``: 0 ``orv_attention_fwd`` without vT, 1 with vT, 2 ``_bounded``, 3 ``_packed``, 4 ``_bounded_dev``."""
+    import ctypes
+    buf = ctypes.create_string_buffer(96)
+    check(lib().orv_attention_kernel_name(int(entry), int(B), int(S), int(H), float(scale), float(score_bound), int(bool(aligned_out)), buf, 96),
+          "orv_attention_kernel_name")
+    return buf.value.decode()
+
+
 def attention_packed_ok(score_bound, scale) -> bool:
     """Can ``attention_fwd(..., out_packed=True)`` run this call?  (Only the shift-free ping-pong kernel writes the packed layout.)"""
     return (score_bound is not None and 0.0 < float(score_bound) <= float(lib().orv_attention_static_limit(1))
