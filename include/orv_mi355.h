@@ -721,6 +721,39 @@ int orv_pc_normals(const float* points, const int* idx, int N, int k, double cam
  * normal becomes (camera - p) / |camera - p|, or (0, 0, 1) when that is zero too; any other is negated when n . (camera - p) < 0. */
 int orv_pc_orient(const float* points, const float* normals, int N, double camx, double camy, double camz, float* out, void* stream);
 
+/* -- Label-map compositing: segmentation masks to the 2-D label image and its colour preview ---------------------------------------------
+ * Replaces the last non-network step of ORV's label preparation, _postprocess_labels (orv/dataset/prepare_dataset.py:1377-1486), which
+ * copies [n, H, W] booleans to the host, writes them to disk, reloads them in a 16-process pool and runs 2 n boolean-index stores per
+ * frame.  The contract is written out in DESIGN.md section 18.  PARITY UNPINNED for the two supervision definitions (area as the count of
+ * set pixels, mask_to_xyxy as the inclusive bounding box, zeros for an empty mask): supervision is not installed where this was written.
+ *   masks    F x n planes of H x W pixels, 1 <= H, W < 65536, behind one device pointer; plane (f, j) starts at element f stride_f +
+ *            j stride_n (any non-negative element strides below 2^40: a permuted or sliced view needs no copy) and is contiguous.
+ *            mask_bytes = 1: bool or uint8, a pixel is set where the byte is nonzero; the pointer may be any byte address.
+ *            mask_bytes = 4: fp32 logits, 4-byte aligned, a pixel is set where x > threshold in IEEE terms, decided on the bits so that
+ *            the device's denormal mode has no say: +-0 and NaN are not above 0, the smallest denormal and +inf are; a NaN threshold
+ *            sets nothing.
+ * Nothing outside a plane is read: a row or group that is not 16-byte aligned, and the last partial group, are read element by element.
+ * Every value is an integer and there are no atomics: bit-reproducible.  Every argument is checked before any launch and no device
+ * pointer is followed; F = 0 or n = 0 launches nothing that reads a mask.
+ *
+ * Per (frame, mask) plane (replaces sv.mask_to_xyxy and detections.area, prepare_dataset.py:1406-1420, and for logits the threshold of
+ * :1275-1279): area int64 [F, n] = the count of set pixels, xyxy int64 [F, n, 4] = x_min, y_min, x_max, y_max, inclusive, over the set
+ * pixels, all zeros for an empty mask.  bands in [1, H] row bands per plane, a workgroup each, write one record of five int32 to
+ * workspace int32 [F n bands 5] (the caller's; no initial value is needed); a second launch combines a plane's records in band order. */
+int orv_lm_mask_stats(const void* masks, int mask_bytes, int F, int n, int H, int W, long stride_f, long stride_n, float threshold,
+                      int bands, int* workspace, long* area, long* xyxy, void* stream);
+/* Per frame (replaces the two paint loops of prepare_dataset.py:1412-1444; the threshold of :1275-1279 for logits): index uint8 [F, H, W]
+ * starts at 255 and color uint8 [F, H, W, 3] at 0; for k = 0 .. m - 1 in sequence, where mask j = order[k] is set, index = label_ids[j] and
+ * color = palette[label_ids[j] % 60].  A pixel painted with id 255 is painted and gets its colour: the kernel carries a painted flag per
+ * pixel and never tests index == 255.  order int [m] (m <= n, entries in [0, n), expected distinct; a repeated entry repaints), label_ids
+ * uint8 [n] and palette uint8 [60, 3] (written in the order given: the caller arranges b, g, r) are HOST arrays, read during the call;
+ * steps uint32 [m + 256] is the caller's device scratch, which the call fills stream-ordered with the paint steps and the id -> triple
+ * table.  index and color are 16-byte aligned.  One lane owns 16 consecutive pixels; traffic is F m H W mask_bytes read and 4 F H W
+ * written.  F = 0 launches nothing. */
+int orv_lm_compose(const void* masks, int mask_bytes, int F, int n, int H, int W, long stride_f, long stride_n, float threshold,
+                   const int* order, int m, const unsigned char* label_ids, const unsigned char* palette, unsigned* steps,
+                   unsigned char* index, unsigned char* color, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,8 @@ SIGNATURES = {
     "orv_pc_outlier": (c_int, [c_void_p, c_int, c_int, c_double] + [c_void_p] * 4 + [c_long, c_void_p]),
     "orv_pc_normals": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_double] * 3 + [c_void_p, c_void_p]),
     "orv_pc_orient": (c_int, [c_void_p, c_void_p, c_int] + [c_double] * 3 + [c_void_p, c_void_p]),
+    "orv_lm_mask_stats": (c_int, [c_void_p] + [c_int] * 5 + [c_long, c_long, c_float, c_int] + [c_void_p] * 4),
+    "orv_lm_compose": (c_int, [c_void_p] + [c_int] * 5 + [c_long, c_long, c_float, c_void_p, c_int] + [c_void_p] * 6),
 }
 
 _lib = None

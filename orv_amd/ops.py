@@ -1216,3 +1216,52 @@ def pc_orient(points, normals, camera):
     out = torch.empty_like(normals)
     check(lib().orv_pc_orient(_p(points), _p(normals), N, *[float(c) for c in camera], _p(out), _stream()), "orv_pc_orient")
     return out
+
+
+# ---- label-map compositing (csrc/labelmap.hip) ----
+LM_DTYPES = {torch.bool: 1, torch.uint8: 1, torch.float32: 4}
+
+
+def _lm_planes(masks, who):
+    """masks [F,n,H,W] bool / uint8 / fp32 on the GPU whose inner [H,W] plane is contiguous -> (bytes per pixel, F, n, H, W, stride_f, stride_n)."""
+    if not isinstance(masks, torch.Tensor) or masks.dtype not in LM_DTYPES:
+        raise RuntimeError(f"orv_amd.ops: `masks` must be a torch.bool, torch.uint8 or torch.float32 tensor (got {getattr(masks, 'dtype', type(masks).__name__)})")
+    _need(masks, masks.dtype, "masks")
+    if masks.dim() != 4:
+        raise ValueError(f"{who}: masks must be [F,n,H,W] (got {tuple(masks.shape)})")
+    F, n, H, W = masks.shape
+    if masks.numel() and ((W > 1 and masks.stride(3) != 1) or (H > 1 and masks.stride(2) != W)):
+        raise ValueError(f"{who}: the inner [H,W] plane of `masks` must be contiguous (strides {masks.stride()})")
+    return LM_DTYPES[masks.dtype], F, n, H, W, masks.stride(0) if F > 1 else 0, masks.stride(1) if n > 1 else 0
+
+
+def lm_mask_stats(masks, threshold=0.0):
+    """masks [F,n,H,W] -> (area int64 [F,n], xyxy int64 [F,n,4]): the count of set pixels and their inclusive box, zeros for an empty mask."""
+    mb, F, n, H, W, sf, sn = _lm_planes(masks, "lm_mask_stats")
+    dev = masks.device
+    area, xyxy = torch.empty(F, n, dtype=torch.int64, device=dev), torch.empty(F, n, 4, dtype=torch.int64, device=dev)
+    bands = min(max(H, 1), max(1, -(-1024 // max(F * n, 1))))          # about a thousand workgroups when the planes are few
+    ws = torch.empty(max(F * n * bands * 5, 1), dtype=torch.int32, device=dev)
+    with _timed(("lm_mask_stats", mb, F, n, H, W)):
+        check(lib().orv_lm_mask_stats(_p(masks), mb, F, n, H, W, sf, sn, float(threshold), bands, _p(ws), _p(area), _p(xyxy), _stream()),
+              "orv_lm_mask_stats")
+    return area, xyxy
+
+
+def lm_compose(masks, order, label_ids, palette, threshold=0.0):
+    """masks [F,n,H,W]; ``order`` a sequence of m <= n mask numbers, ``label_ids`` n values in [0, 255], ``palette`` 60 triples in the
+    channel order to be written (all on the host) -> (index uint8 [F,H,W], color uint8 [F,H,W,3])."""
+    mb, F, n, H, W, sf, sn = _lm_planes(masks, "lm_compose")
+    order, label_ids, palette = [int(j) for j in order], [int(v) for v in label_ids], [int(v) for t in palette for v in t]
+    if len(label_ids) != n or any(not 0 <= v <= 255 for v in label_ids):
+        raise ValueError(f"lm_compose: label_ids must hold n = {n} values in [0, 255]")
+    if len(palette) != 180 or any(not 0 <= v <= 255 for v in palette):
+        raise ValueError("lm_compose: palette must hold 60 triples of values in [0, 255]")
+    m, dev = len(order), masks.device
+    index, color = torch.empty(F, H, W, dtype=torch.uint8, device=dev), torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    steps = torch.empty(m + 256, dtype=torch.int32, device=dev)
+    with _timed(("lm_compose", mb, F, n, m, H, W)):
+        check(lib().orv_lm_compose(_p(masks), mb, F, n, H, W, sf, sn, float(threshold), (ctypes.c_int * max(m, 1))(*order), m,
+                                   (ctypes.c_ubyte * max(n, 1))(*label_ids), (ctypes.c_ubyte * 180)(*palette), _p(steps), _p(index), _p(color),
+                                   _stream()), "orv_lm_compose")
+    return index, color
