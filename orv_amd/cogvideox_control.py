@@ -32,7 +32,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 import torch
 from torch import nn
 
-from . import _state, lora as _lora, ops
+from . import _state, lora as _lora, ops, stages, training as _training
 from .components import ActionEmbed, ActionRecon, Transformer3DModelTrajOutput
 from .embeddings import sincos_3d
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler, retrieve_timesteps
@@ -736,14 +736,6 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
                                           w_out=arr([no.weight]), b_out=arr([no.bias])))
         return self._ptr_tables[1]
 
-    def _linear_k64(self, x2d, lin):
-        """A and W of a GEMM whose K is not a multiple of 64 (only tiny test configs) get zero-padded."""
-        W, K = lin.weight.reshape(lin.weight.shape[0], -1), x2d.shape[1]
-        if K % 64:
-            pad = 64 - K % 64
-            x2d, W = torch.nn.functional.pad(x2d, (0, pad)), torch.nn.functional.pad(W, (0, pad))
-        return x2d.contiguous(), W.contiguous()
-
     def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor,
                 controls_or_guidances: Dict[str, torch.Tensor], timestep: Union[int, float, torch.LongTensor],
                 timestep_cond: Optional[torch.Tensor] = None, ofs: Optional[Union[int, float, torch.LongTensor]] = None,
@@ -771,8 +763,7 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
             # hand-written backward attached to autograd as one node
             if self._lora_fused is not None:
                 raise RuntimeError("an adapter is fused into the weights: unfuse_lora() before a forward that records gradients")
-            from .training import forward_with_grad
-            out, mask, recon = forward_with_grad(self, hidden_states, encoder_hidden_states, controls_or_guidances, timestep,
+            out, mask, recon = _training.forward_with_grad(self, hidden_states, encoder_hidden_states, controls_or_guidances, timestep,
                                                  ofs, image_rotary_emb, num_views, image_rotary_emb_view, lora=lora_rt)
             if not return_dict:
                 return (out, mask, recon)
@@ -783,22 +774,13 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
 
     # ---- multiview (:273-348, :797-800) ----
     def _mv_state(self, b, v, f, Nt, P, S, dev):
-        """Workspace + the token permutation '(b v) (f s) -> (b f) (v s)' (text '(b v) n -> (b f) (v n)') as a row index
-        into the joint [(b v), S, D] buffer, built once per shape."""
+        """Per-shape cache of the multiview regrouping: ``stages.mv_layout`` (row index, sizes) plus the workspace of ``_mv_block``."""
         key = ("mv", b, v, f, Nt, P, str(dev))
         if key not in self._ws:
-            D, H = self.inner_dim, self.config.num_attention_heads
-            Sm = v * (Nt + P)
-            bi = torch.arange(b, device=dev).view(b, 1, 1, 1)
-            fi = torch.arange(f, device=dev).view(1, f, 1, 1)
-            vi = torch.arange(v, device=dev).view(1, 1, v, 1)
-            txt = ((bi * v + vi) * S + torch.arange(Nt, device=dev).view(1, 1, 1, Nt)).expand(b, f, v, Nt)
-            vid = (bi * v + vi) * S + Nt + fi * P + torch.arange(P, device=dev).view(1, 1, 1, P)
-            idx = torch.cat([txt.reshape(b, f, v * Nt), vid.reshape(b, f, v * P)], dim=2).to(torch.int32).contiguous()
-            s_pad = (Sm + 63) // 64 * 64
-            R = b * f * Sm
+            D = self.inner_dim
+            lay = stages.mv_layout(b, v, f, Nt, P, S, dev)
             e = lambda *shape: torch.empty(*shape, dtype=BF16, device=dev)
-            self._ws[key] = dict(idx=idx.view(-1), xm=e(R, D), qkv=e(R, 3 * D), att=e(R, D), s_pad=s_pad, Sm=Sm, R=R)
+            self._ws[key] = dict(lay, xm=e(lay["R"], D), qkv=e(lay["R"], 3 * D), att=e(lay["R"], D))
         return self._ws[key]
 
     def _mv_pointer_tables(self, dev):
@@ -892,147 +874,30 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
 
     def _forward_inference(self, hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs,
                            image_rotary_emb, return_dict, num_views=1, image_rotary_emb_view=None, lora=None):
+        """Workspace lookup -> ``stages.embed`` -> score-bound priming -> blocks -> ``stages.head``."""
         c = self.config
-        dev = hidden_states.device
-        if num_views > 1:                                                            # :756-758
-            bb, vf = hidden_states.shape[:2]
-            hidden_states = hidden_states.reshape(bb * num_views, vf // num_views, *hidden_states.shape[2:])
-            encoder_hidden_states = encoder_hidden_states.repeat_interleave(num_views, dim=0)
-        B, T, C, Hh, Ww = hidden_states.shape
-        p, pt = c.patch_size, c.patch_size_t
-        D, heads, E = self.inner_dim, c.num_attention_heads, c.time_embed_dim
-        mod_text = bool(c.modulate_encoder_hidden_states)
-        Nt = encoder_hidden_states.shape[1] if mod_text else 0
-        Tq = T // (pt or 1)
-        P = (Hh // p) * (Ww // p)
-        Nv = Tq * P
-        S = Nt + Nv
-        ws = self._workspace(B, S, Nv, dev)
-        x, xn, qkv, att, hbuf, s_pad = ws["x"], ws["xn"], ws["qkv"], ws["att"], ws["h"], ws["s_pad"]
-        packed = ws["packed"]
+        sh = stages.shapes(hidden_states, encoder_hidden_states, num_views, c)
+        B, S, Nt, D, M, T = sh.B, sh.S, sh.Nt, sh.D, sh.M, sh.T
+        ws = self._workspace(B, S, sh.Nv, hidden_states.device)
+        x, xn, hbuf, packed = ws["x"], ws["xn"], ws["h"], ws["packed"]
+        st = stages.embed(self, sh, x, hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs, image_rotary_emb,
+                          image_rotary_emb_view)
+        mod, grp, rope, mv = st.mod, st.grp, st.rope, st.mv
 
-        # 1. time (+ofs) embedding  (:762-775)
-        tvec = torch.as_tensor(timestep, device=dev).reshape(-1).to(torch.float32)
-        if tvec.numel() == 1 and B // num_views > 1:
-            tvec = tvec.expand(B // num_views)
-        te = self.time_embedding
-        t_emb = ops.timestep_embedding(tvec.contiguous(), D, c.flip_sin_to_cos, c.freq_shift)
-        temb = ops.skinny_linear(ops.skinny_linear(t_emb, te.linear_1.weight, te.linear_1.bias, act_out="silu"),
-                                 te.linear_2.weight, te.linear_2.bias)
-        if self.ofs_embedding is not None:
-            oe = self.ofs_embedding
-            ovec = torch.as_tensor(ofs, device=dev).reshape(-1).to(torch.float32)
-            o_emb = ops.timestep_embedding(ovec.contiguous(), c.ofs_embed_dim, c.flip_sin_to_cos, c.freq_shift)
-            o_emb = ops.skinny_linear(ops.skinny_linear(o_emb, oe.linear_1.weight, oe.linear_1.bias, act_out="silu"),
-                                      oe.linear_2.weight, oe.linear_2.bias)
-            temb = temb + o_emb          # [B,E] + [1,E]; tiny glue add in the model dtype as at :775
-        if num_views > 1:                # multiviews share the same noise level (:777-779)
-            temb = temb.repeat_interleave(num_views, dim=0).contiguous()
-
-        # 2. patch embedding straight into the joint [B,S,D] buffer (:788-794)
-        pe = self.patch_embed
-        tokens = ops.patchify(hidden_states.to(BF16), None, p, pt)
-        a2, w2 = self._linear_k64(tokens.view(B * Nv, -1), pe.proj)
-        pos = pe.video_pos_table(T, Hh, Ww, dev)
-        pos_mod = Nv
-        if num_views > 1:
-            # :797-800 adds pos_embedding_v[view, spatial] to every frame: folded into the patch-embed epilogue as one table
-            # of n_view*Nv rows (row = view*Nv + frame*P + s), built once per shape.
-            pos, pos_mod = self._view_pos_table(pos, num_views, T, P, dev), num_views * Nv
-        ops.gemm(a2, w2, pe.proj.bias, x, B * Nv, D, a2.shape[1], epilogue=2 if pos is not None else 0, R=pos, r_mod=pos_mod,
-                 ldr=D, cmap=ops.rowmap(Nv, S, Nt))
-        if mod_text:
-            a2, w2 = self._linear_k64(encoder_hidden_states.to(BF16).reshape(B * Nt, -1), pe.text_proj)
-            ops.gemm(a2, w2, pe.text_proj.bias, x, B * Nt, D, a2.shape[1], cmap=ops.rowmap(Nt, S, 0))
-
-        # 3. action embedding (:805-825)
-        action_emb = is_action_mask = actions_recon = None
-        actions = controls_or_guidances.get('actions', None)
-        if actions is not None:
-            actions = actions.to(device=dev)
-            res = (actions.size(1) + 1) % 4
-            pad_frames = 4 - res if res > 0 else 0
-            if pad_frames:
-                actions = torch.cat([actions.new_zeros((actions.shape[0], pad_frames, actions.shape[2])), actions], dim=1)
-            action_emb, is_action_mask = self.action_embed(actions)
-            if num_views > 1:            # multiviews share the same actions (:815-816)
-                action_emb = action_emb.repeat_interleave(num_views, dim=0)
-            if self.training and c.recon_action and self.action_recon is not None:
-                actions_recon = self.action_recon(action_emb)
-                if pad_frames > 0:
-                    actions_recon = actions_recon[:, pad_frames:]
-        # 3b. occupancy-derived visual guidance (:828-858): each control map goes through the SAME patch-embed (+ pos table),
-        #     initial_combine_linear(hidden.repeat(1,1,K) + cat(controls)) is added to the video rows.  The reference also
-        #     runs text_proj for every control map and throws the result away (:833,:842) - not reproduced.
-        ctrl_toks = []
-        if c.visual_guidance:
-            for key in ('depths', 'labels'):
-                cm = controls_or_guidances.get(key, None)
-                if cm is None:
-                    continue
-                if num_views > 1:
-                    cm = cm.reshape(cm.shape[0] * num_views, cm.shape[1] // num_views, *cm.shape[2:])
-                tk = ops.patchify(cm.to(device=dev, dtype=BF16), None, p, pt)
-                a2c, w2c = self._linear_k64(tk.view(B * Nv, -1), pe.proj)
-                ctok = torch.empty(B * Nv, D, dtype=BF16, device=dev)
-                cpos = pe.video_pos_table(T, Hh, Ww, dev)      # controls get the frame table only (:828-858)
-                ops.gemm(a2c, w2c, pe.proj.bias, ctok, B * Nv, D, a2c.shape[1], epilogue=2 if cpos is not None else 0,
-                         R=cpos, r_mod=Nv, ldr=D)
-                ctrl_toks.append(ctok)
-        if ctrl_toks:
-            assert len(ctrl_toks) == self.num_control_keys, \
-                f'Mismatched number of controls: {len(ctrl_toks)=} but {self.num_control_keys=}.'
-            K2 = self.num_control_keys * D
-            comb = torch.empty(B * Nv, K2, dtype=BF16, device=dev)
-            vmap = ops.rowmap(Nv, S, Nt)
-            for jx, ctok in enumerate(ctrl_toks):
-                ops.add_rows(x, vmap, ctok, comb, jx * D, B * Nv, D, ldo=K2)
-            icl = self.initial_combine_linear
-            ops.gemm(comb, icl.weight, icl.bias, x, B * Nv, D, K2, epilogue=2, R=x, ldr=D, cmap=vmap)
-
-        # 4. modulation tables for every norm, fp32 [B, G, 3D]: group 0 = text rows, 1.. = frames (:117-145)
-        Ta = action_emb.shape[1] if action_emb is not None else 1
-        if Nv % Ta:
-            raise ValueError(f"{Nv} video tokens cannot be split over {Ta} action frames")
-        per_group = Nv // Ta if action_emb is not None else 0
-        G = 1 + Ta
-        grp = ops.groups(S, Nt, per_group)
-        L = c.num_layers
-        a3d = action_emb.contiguous() if action_emb is not None else None
-        ptr = self._pointer_tables(dev)
-        mod = ops.modulation_tables(temb, a3d, ptr["w_blk"], ptr["b_blk"], 2 * L, B, Ta, E, 3 * D, mod_text)
-        modf = ops.modulation_tables(temb, a3d, ptr["w_out"], ptr["b_out"], 1, B, Ta, E, 2 * D, False)[0]
-
-        rope = None
-        if image_rotary_emb is not None:
-            rope = tuple(r.to(device=dev, dtype=torch.float32).contiguous() for r in image_rotary_emb)
-        mv = mv_mod = rope_view = None
-        if c.multiview:
-            if Nv % T:
-                raise ValueError(f"{Nv} video tokens cannot be split over {T} frames for the multiview blocks")
-            mv = self._mv_state(B // num_views, num_views, T, Nt, Nv // T, S, dev)
-            wmv, bmv = self._mv_pointer_tables(dev)
-            mv_mod = ops.modulation_tables(temb, None, wmv, bmv, L, B, 1, E, 3 * D, mod_text)       # [L, B, 2, 3D]
-            grp0 = ops.groups(S, Nt, 0)
-            if image_rotary_emb_view is not None:
-                rope_view = tuple(r.to(device=dev, dtype=torch.float32).contiguous() for r in image_rotary_emb_view)
-
-        # 5. transformer blocks (:861-907 -> :394-445)
-        M = B * S
-        mb, mg = G * 3 * D, 3 * D
+        # transformer blocks (:861-907 -> :394-445)
+        mb, mg = sh.G * 3 * D, 3 * D
         scale = 1.0 / math.sqrt(c.attention_head_dim)
         prime_score_bounds([b.attn1 for b in self.transformer_blocks], scale, rope=rope is not None)
         if mv is not None:
-            prime_score_bounds([b.attn1 for b in self.mv_blocks], scale, rope=rope_view is not None)
+            prime_score_bounds([b.attn1 for b in self.mv_blocks], scale, rope=st.rope_view is not None)
         mxw = self._mxfp8_weights() if self._mxfp8 else None
         for i, blk in enumerate(self.transformer_blocks):
             if mv is not None:
-                self._mv_block(self.mv_blocks[i], mv, mv_mod[i], x, xn, grp0, B, S, Nt, num_views, T, rope_view)
+                self._mv_block(self.mv_blocks[i], mv.ws, mv.mod[i], x, xn, mv.grp0, B, S, Nt, num_views, T, st.rope_view)
             m1, m2 = mod[2 * i], mod[2 * i + 1]
             if mxw is not None:
                 self._mx_block(blk, mxw[i], ws, m1, m2, mb, mg, grp, B, S, Nt, rope, scale)
                 continue
-            at = blk.attn1
             lbw = lora.block(i) if lora is not None else None
             if lbw is not None:
                 self._lora_attention(blk, lbw, lora, ws, m1, mb, mg, grp, B, S, Nt, rope, scale)
@@ -1045,32 +910,10 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
             ops.gemm(hbuf, f2.weight, f2.bias, x, M, D, f0.weight.shape[0], epilogue=2, R=x, ldr=D,
                      gate=m2[..., 2 * D:], gate_b=mb, gate_g=mg, grp=grp, a_packed=packed["ffn"])
 
-        # 6. head: norm_final is row-wise, so the 2B (:916) and 5B (:911-913) branches are the same arithmetic on the
-        #    video rows; read them in place from the joint buffer.
-        vis, vis2 = ws["vis"], ws["vis2"]
-        gv = ops.groups(Nv, 0, per_group)
-        ops.layernorm_modulate(x, vis, self.norm_final.weight, self.norm_final.bias, None, None, 0, 0, gv, B, D,
-                               c.norm_eps, xmap=ops.rowmap(Nv, S, Nt))
-        no = self.norm_out
-        ops.layernorm_modulate(vis, vis2, no.norm.weight, no.norm.bias, modf[..., D:], modf[..., :D], G * 2 * D, 2 * D,
-                               gv, B, D, c.norm_eps)
-        fo = self.proj_out.weight.shape[0]
-        wo, bo = self.proj_out.weight, self.proj_out.bias
-        if fo % 64:
-            padn = 64 - fo % 64
-            wo = torch.nn.functional.pad(wo, (0, 0, 0, padn)).contiguous()
-            bo = torch.nn.functional.pad(bo, (0, padn)).contiguous() if bo is not None else None
-        out_tok = torch.empty(B * Nv, wo.shape[0], dtype=BF16, device=dev)
-        ops.gemm(vis2, wo, bo, out_tok, B * Nv, wo.shape[0], D)
-        if wo.shape[0] != fo:
-            out_tok = out_tok[:, :fo].contiguous()
-        output = ops.unpatchify(out_tok, B, T, fo // (p * p * (pt or 1)), Hh, Ww, p, pt)
-        if num_views > 1:                                                            # :941
-            output = output.reshape(B // num_views, num_views * T, *output.shape[2:])
-
+        output, _ = stages.head(self, sh, x, ws["vis"], ws["vis2"], st.modf)
         if not return_dict:
-            return (output, is_action_mask, actions_recon)
-        return Transformer3DModelTrajOutput(sample=output, is_action_mask=is_action_mask, actions_recon=actions_recon)
+            return (output, st.is_action_mask, st.actions_recon)
+        return Transformer3DModelTrajOutput(sample=output, is_action_mask=st.is_action_mask, actions_recon=st.actions_recon)
 
 
 # ------------------------------------------------------------------------------------------------------------------

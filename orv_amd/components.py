@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from . import ops
+from .stages import mlp2
 
 
 @dataclass
@@ -53,9 +53,7 @@ class ActionEmbed(nn.Module):
         if self.patch_size_t > 1:
             x = x.reshape(B, x.shape[1] // self.patch_size_t, -1)
         frames = x.shape[1]
-        w0, w3 = self.mlp[0], self.mlp[3]
-        h = ops.skinny_linear(x.reshape(B * frames, -1).to(torch.bfloat16), w0.weight, w0.bias, act_out="gelu_tanh")
-        emb = ops.skinny_linear(h, w3.weight, w3.bias).view(B, frames, -1)
+        emb = mlp2(x.reshape(B * frames, -1).to(torch.bfloat16), self.mlp[0], self.mlp[3], "gelu_tanh")[0].view(B, frames, -1)
         if self.forced_mask is not None:
             if self.forced_mask.device != x.device or self.forced_mask.dtype != torch.bool:
                 self.forced_mask = self.forced_mask.to(device=x.device, dtype=torch.bool)   # once: no H2D copy per call
@@ -79,9 +77,7 @@ class ActionRecon(nn.Module):
 
     def forward(self, x: torch.Tensor):
         B, F, _ = x.shape
-        h = ops.skinny_linear(x.reshape(B * F, -1).contiguous(), self.mlp[0].weight, self.mlp[0].bias,
-                              act_out="gelu_tanh")
-        y = ops.skinny_linear(h, self.mlp[2].weight, self.mlp[2].bias).view(B, F, -1)
+        y = mlp2(x.reshape(B * F, -1).contiguous(), self.mlp[0], self.mlp[2], "gelu_tanh")[0].view(B, F, -1)
         if self.compress_ratio > 1:
             y = y.reshape(B, int(F * self.compress_ratio), y.shape[-1] // self.compress_ratio).contiguous()
         return y[:, 1:]

@@ -268,7 +268,6 @@ def unpack_rows16(src, M, K, dst=None, ld_dst=None):
 
 def gemm_kernel_name(M, N, K, epilogue=0, a_packed=False, c_packed=False) -> Optional[str]:
     """Kernel symbol ``gemm`` launches for this call, or None when no kernel takes the packed-operand combination."""
-    import ctypes
     buf = ctypes.create_string_buffer(96)
     if a_packed or c_packed:
         rc = lib().orv_gemm_kernel_name_packed(M, N, K, epilogue, int(bool(a_packed)), int(bool(c_packed)), buf, 96)
@@ -324,7 +323,6 @@ def attention_ws_bytes(B, S, H):
 def attention_kernel_name(entry, B, S, H, scale, score_bound=0.0, aligned_out=True) -> str:
     """Kernel symbol(s) a forward-attention entry point launches for this call (``orv_attention_kernel_name``; no GPU work).
     ``entry``: 0 ``orv_attention_fwd`` without vT, 1 with vT, 2 ``_bounded``, 3 ``_packed``, 4 ``_bounded_dev``."""
-    import ctypes
     buf = ctypes.create_string_buffer(96)
     check(lib().orv_attention_kernel_name(int(entry), int(B), int(S), int(H), float(scale), float(score_bound), int(bool(aligned_out)), buf, 96),
           "orv_attention_kernel_name")
@@ -860,7 +858,6 @@ def gs_render(ranges, point_list, xy, conic_opacity, depth, colors, features, bg
 # ---- point-cloud voxelization (voxelize.hip) ----
 def voxel_grid_size(voxel_size, coors_range):
     """Cells per axis (x, y, z) of ``coors_range`` [6] cut into ``voxel_size`` [3] (fp32 values): round((hi - lo) / vs) in fp32.  Host only."""
-    import ctypes
     grid = (ctypes.c_int * 3)()
     check(lib().orv_voxel_grid_size(*[float(v) for v in voxel_size], *[float(v) for v in coors_range], ctypes.addressof(grid)),
           "orv_voxel_grid_size")

@@ -14,13 +14,14 @@ its activations with plain torch ops on those few-kB tensors; all matmuls, inclu
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from typing import Dict, List, Optional
 
 import torch
 
-from . import _state, lora as _lora, ops
+from . import _state, cogvideox_control as _model, lora as _lora, ops, stages
 
 _SCATTER_GRADS = os.environ.get("ORV_SCATTER_GRADS", "1") != "0"      # A/B switch (small gradients: arena -> flat buffer directly)
 
@@ -101,14 +102,6 @@ def _wgrad(dY2d, X2d, dW, M, N, K, accumulate=True, bias_sum=None):
             dW.copy_(tmp[:, :K])
 
 
-def _pad_k(a, w):
-    K = a.shape[1]
-    if K % 64:
-        pad = 64 - K % 64
-        a, w = torch.nn.functional.pad(a, (0, pad)), torch.nn.functional.pad(w, (0, pad))
-    return a.contiguous(), w.contiguous()
-
-
 def _dgrad(dY2d, W, dX, M, N, K, epilogue=0, R=None):
     """dX[M,K] = dY[M,N] . W[N,K]  (contraction over N) via W^T [K, N_pad]."""
     WT = ops.transpose(W.detach().contiguous(), N, K)          # [K, N_pad]
@@ -138,14 +131,13 @@ def _attn_forward(at, xn, ly, bufs, B_, S_, n_text, heads, rope, scale, lbw=None
     D = heads * 64
     M_ = B_ * S_
     dev = xn.device
-    from .cogvideox_control import CogVideoXTransformer3DModelTraj as _M
     ly.qkv_raw = torch.empty(M_, 3 * D, dtype=BF16, device=dev)       # raw projection: input of the qk-LayerNorm adjoint
     ly.qkvn = torch.empty(M_, 3 * D, dtype=BF16, device=dev)          # q' | k' | v as the attention kernels read them (kept:
     if lbw is not None and lbw.nT:
         ly.lora_t = torch.empty(M_, lbw.nT * lora.rp, dtype=BF16, device=dev)
         _lora.qkv_projection(at, lbw, lora, xn, ly.qkvn, ly.lora_t, rope, B_, S_, heads, n_text, bufs.s_pad, scale, raw=ly.qkv_raw)
     else:
-        _M._qkv_projection(at, xn, ly.qkvn, rope, B_, S_, heads, n_text, bufs.s_pad, scale, raw=ly.qkv_raw)   # 148 MB/layer)
+        _model.CogVideoXTransformer3DModelTraj._qkv_projection(at, xn, ly.qkvn, rope, B_, S_, heads, n_text, bufs.s_pad, scale, raw=ly.qkv_raw)   # 148 MB/layer)
     ly.att = torch.empty(M_, D, dtype=BF16, device=dev)
     ly.lse = torch.empty(B_, heads, S_, dtype=torch.float32, device=dev)
     ops.attention_fwd(ly.qkvn, None, ly.att, B_, S_, heads, bufs.s_pad, 1.0 / LOG2E, lse=ly.lse, score_bound_dev=at.score_bound_dev(scale))
@@ -206,196 +198,37 @@ def _attn_backward(at, ly, xn, datt, bufs, B_, S_, n_text, heads, rope, scale, g
     return dxn
 
 
-def _mv_index(b, v, f, Nt, P, S, dev):
-    """Row index of the '(b v) (f s) -> (b f) (v s)' regrouping (text '(b v) n -> (b f) (v n)'), as in
-    ``CogVideoXTransformer3DModelTraj._mv_state``."""
-    bi = torch.arange(b, device=dev).view(b, 1, 1, 1)
-    fi = torch.arange(f, device=dev).view(1, f, 1, 1)
-    vi = torch.arange(v, device=dev).view(1, 1, v, 1)
-    txt = ((bi * v + vi) * S + torch.arange(Nt, device=dev).view(1, 1, 1, Nt)).expand(b, f, v, Nt)
-    vid = (bi * v + vi) * S + Nt + fi * P + torch.arange(P, device=dev).view(1, 1, 1, P)
-    return torch.cat([txt.reshape(b, f, v * Nt), vid.reshape(b, f, v * P)], dim=2).to(torch.int32).contiguous().view(-1)
-
-
 def forward_train(model, hidden_states, encoder_hidden_states, controls, timestep, ofs=None, image_rotary_emb=None,
                   num_views=1, image_rotary_emb_view=None, lora=None):
-    """Same arithmetic as ``CogVideoXTransformer3DModelTraj.forward`` (inference kernels), keeping what backward needs."""
+    """``stages.embed(keep=sv)`` -> score-bound priming -> ``run_block`` loop -> ``stages.head``: the stages and kernels of
+    ``CogVideoXTransformer3DModelTraj._forward_inference``, keeping what backward needs (the one arithmetic difference: ``stages.mlp2``)."""
     c = model.config
     dev = hidden_states.device
-    nv_ = num_views
-    if nv_ > 1:                                                                      # :756-758
-        bb, vf = hidden_states.shape[:2]
-        hidden_states = hidden_states.reshape(bb * nv_, vf // nv_, *hidden_states.shape[2:])
-        encoder_hidden_states = encoder_hidden_states.repeat_interleave(nv_, dim=0)
-    B, T, C, Hh, Ww = hidden_states.shape
-    b0 = B // nv_
-    p, pt = c.patch_size, c.patch_size_t
-    D, heads, E = model.inner_dim, c.num_attention_heads, c.time_embed_dim
-    mod_text = bool(c.modulate_encoder_hidden_states)
-    Nt = encoder_hidden_states.shape[1] if mod_text else 0
-    Tq = T // (pt or 1)
-    P = (Hh // p) * (Ww // p)
-    Nv = Tq * P
-    S = Nt + Nv
-    M = B * S
     sv = _Saved()
-    sv.dims = dict(B=B, T=T, Hh=Hh, Ww=Ww, D=D, heads=heads, E=E, Nt=Nt, Nv=Nv, S=S, M=M, P=P, mod_text=mod_text, nv=nv_,
-                   b0=b0)
+    sh = stages.shapes(hidden_states, encoder_hidden_states, num_views, c)
+    B, S, Nt, D, M, heads = sh.B, sh.S, sh.Nt, sh.D, sh.M, sh.heads
     e = lambda *shape, dt=BF16: torch.empty(*shape, dtype=dt, device=dev)
-
-    # conditioning branch (tiny): matmuls in HIP, activations' adjoints later via torch on [B, T, E] tensors
-    tvec = torch.as_tensor(timestep, device=dev).reshape(-1).to(torch.float32)
-    if tvec.numel() == 1 and b0 > 1:
-        tvec = tvec.expand(b0)
-    te = model.time_embedding
-    sv.t_emb = ops.timestep_embedding(tvec.contiguous(), D, c.flip_sin_to_cos, c.freq_shift)
-    sv.te_u1 = ops.skinny_linear(sv.t_emb, te.linear_1.weight, te.linear_1.bias)                 # pre-SiLU
-    sv.te_h1 = torch.nn.functional.silu(sv.te_u1.float()).to(BF16)
-    temb = ops.skinny_linear(sv.te_h1, te.linear_2.weight, te.linear_2.bias)
-    sv.has_ofs = model.ofs_embedding is not None
-    if sv.has_ofs:                                                                   # :771-775
-        oe = model.ofs_embedding
-        ovec = torch.as_tensor(ofs, device=dev).reshape(-1).to(torch.float32)
-        sv.o_emb = ops.timestep_embedding(ovec.contiguous(), c.ofs_embed_dim, c.flip_sin_to_cos, c.freq_shift)
-        sv.oe_u1 = ops.skinny_linear(sv.o_emb, oe.linear_1.weight, oe.linear_1.bias)
-        sv.oe_h1 = torch.nn.functional.silu(sv.oe_u1.float()).to(BF16)
-        temb = temb + ops.skinny_linear(sv.oe_h1, oe.linear_2.weight, oe.linear_2.bias)
-    if nv_ > 1:
-        temb = temb.repeat_interleave(nv_, dim=0).contiguous()
-    sv.temb = temb
-
-    pe = model.patch_embed
-    sv.tokens = ops.patchify(hidden_states.to(BF16), None, p, pt)
     x = e(M, D)
-    a2, w2 = _pad_k(sv.tokens.view(B * Nv, -1), pe.proj.weight.reshape(D, -1))
-    pos = pe.video_pos_table(T, Hh, Ww, dev)
-    cpos = pos
-    pos_mod = Nv
-    if nv_ > 1:
-        pos, pos_mod = model._view_pos_table(pos, nv_, T, P, dev), nv_ * Nv
-    vmap = ops.rowmap(Nv, S, Nt)
-    ops.gemm(a2, w2, pe.proj.bias, x, B * Nv, D, a2.shape[1], epilogue=2 if pos is not None else 0, R=pos, r_mod=pos_mod, ldr=D,
-             cmap=vmap)
-    if mod_text:
-        sv.text2d = encoder_hidden_states.to(BF16).reshape(B * Nt, -1).contiguous()
-        a2, w2 = _pad_k(sv.text2d, pe.text_proj.weight)
-        ops.gemm(a2, w2, pe.text_proj.bias, x, B * Nt, D, a2.shape[1], cmap=ops.rowmap(Nt, S, 0))
+    st = stages.embed(model, sh, x, hidden_states, encoder_hidden_states, controls, timestep, ofs, image_rotary_emb, image_rotary_emb_view,
+                      keep=sv)
+    sv.dims = dataclasses.asdict(sh)
+    mod, grp, rope, rope_view = st.mod, st.grp, st.rope, st.rope_view
 
-    action_emb = is_mask = actions_recon = None
-    actions = controls.get('actions', None)
-    sv.has_actions = actions is not None
-    sv.has_recon = False
-    if actions is not None:
-        actions = actions.to(device=dev)
-        res = (actions.size(1) + 1) % 4
-        padf = 4 - res if res > 0 else 0
-        if padf:
-            actions = torch.cat([actions.new_zeros((actions.shape[0], padf, actions.shape[2])), actions], dim=1)
-        ae = model.action_embed
-        xa = torch.cat([torch.zeros_like(actions[:, :1]), actions], dim=1)
-        xa = xa.reshape(b0, (actions.shape[1] + 1) // ae.compress_ratio, -1)
-        if ae.patch_size_t > 1:
-            xa = xa.reshape(b0, xa.shape[1] // ae.patch_size_t, -1)
-        Ta = xa.shape[1]
-        sv.ae_in = xa.reshape(b0 * Ta, -1).to(BF16).contiguous()
-        sv.ae_u = ops.skinny_linear(sv.ae_in, ae.mlp[0].weight, ae.mlp[0].bias)
-        sv.ae_h = torch.nn.functional.gelu(sv.ae_u.float(), approximate="tanh").to(BF16)
-        emb = ops.skinny_linear(sv.ae_h, ae.mlp[3].weight, ae.mlp[3].bias).view(b0, Ta, E)
-        is_mask = ae.forced_mask.to(dev, torch.bool) if ae.forced_mask is not None else torch.rand(b0, device=dev) < 0.1
-        if ae.mask:
-            emb = torch.where(is_mask[:, None, None], ae.mask_embed.weight[None].to(emb.dtype), emb)
-        sv.is_mask = is_mask
-        if nv_ > 1:                                                                  # :815-816
-            emb = emb.repeat_interleave(nv_, dim=0)
-        action_emb = emb.contiguous()
-        if model.training and c.recon_action and model.action_recon is not None:    # :822-825, components.py:92-104
-            ar = model.action_recon
-            sv.has_recon, sv.ar_pad = True, padf
-            sv.ar_in = action_emb.reshape(B * Ta, E)
-            sv.ar_u = ops.skinny_linear(sv.ar_in, ar.mlp[0].weight, ar.mlp[0].bias)
-            sv.ar_h = torch.nn.functional.gelu(sv.ar_u.float(), approximate="tanh").to(BF16)
-            y = ops.skinny_linear(sv.ar_h, ar.mlp[2].weight, ar.mlp[2].bias).view(B, Ta, -1)
-            if ar.compress_ratio > 1:
-                y = y.reshape(B, int(Ta * ar.compress_ratio), y.shape[-1] // ar.compress_ratio)
-            actions_recon = y[:, 1 + padf:].contiguous()
-    sv.action_emb = action_emb
-
-    # occupancy-derived visual guidance (:828-858)
-    sv.ctrl_tokens = []
-    if c.visual_guidance:
-        ctoks = []
-        for key in ('depths', 'labels'):
-            cm = controls.get(key, None)
-            if cm is None:
-                continue
-            if nv_ > 1:
-                cm = cm.reshape(cm.shape[0] * nv_, cm.shape[1] // nv_, *cm.shape[2:])
-            tk = ops.patchify(cm.to(device=dev, dtype=BF16), None, p, pt)
-            a2c, w2c = _pad_k(tk.view(B * Nv, -1), pe.proj.weight.reshape(D, -1))
-            ctok = e(B * Nv, D)
-            ops.gemm(a2c, w2c, pe.proj.bias, ctok, B * Nv, D, a2c.shape[1], epilogue=2 if cpos is not None else 0, R=cpos,
-                     r_mod=Nv, ldr=D)
-            ctoks.append(ctok)
-            sv.ctrl_tokens.append(tk.view(B * Nv, -1))
-        if ctoks:
-            assert len(ctoks) == model.num_control_keys, \
-                f'Mismatched number of controls: {len(ctoks)=} but {model.num_control_keys=}.'
-            K2 = model.num_control_keys * D
-            sv.comb = e(B * Nv, K2)
-            for jx, ctok in enumerate(ctoks):
-                ops.add_rows(x, vmap, ctok, sv.comb, jx * D, B * Nv, D, ldo=K2)
-            icl = model.initial_combine_linear
-            ops.gemm(sv.comb, icl.weight, icl.bias, x, B * Nv, D, K2, epilogue=2, R=x, ldr=D, cmap=vmap)
-
-    Ta = action_emb.shape[1] if action_emb is not None else 1
-    if Nv % Ta:
-        raise ValueError(f"{Nv} video tokens cannot be split over {Ta} action frames")
-    per_group = Nv // Ta if action_emb is not None else 0
-    G = 1 + Ta
-    sv.dims.update(Ta=Ta, G=G, per_group=per_group)
-    grp = ops.groups(S, Nt, per_group)
-    L = c.num_layers
-    ptr = model._pointer_tables(dev)
-    mod = ops.modulation_tables(temb, action_emb, ptr["w_blk"], ptr["b_blk"], 2 * L, B, Ta, E, 3 * D, mod_text)
-    modf = ops.modulation_tables(temb, action_emb, ptr["w_out"], ptr["b_out"], 1, B, Ta, E, 2 * D, False)[0]
-    sv.mod, sv.modf = mod, modf
-    rope = None
-    if image_rotary_emb is not None:
-        rope = tuple(r.to(device=dev, dtype=torch.float32).contiguous() for r in image_rotary_emb)
-    sv.rope = rope
-    sv.rope_view = None
-    if image_rotary_emb_view is not None:
-        sv.rope_view = tuple(r.to(device=dev, dtype=torch.float32).contiguous() for r in image_rotary_emb_view)
-
-    mb, mg = G * 3 * D, 3 * D
+    mb, mg = sh.G * 3 * D, 3 * D
     scale = 1.0 / math.sqrt(c.attention_head_dim)
-    from .cogvideox_control import prime_score_bounds
-    prime_score_bounds([b.attn1 for b in model.transformer_blocks] + ([b.attn1 for b in model.mv_blocks] if c.multiview else []), scale,
-                       on_device=True)      # no device -> host read in the training step
+    _model.prime_score_bounds([b.attn1 for b in model.transformer_blocks] + ([b.attn1 for b in model.mv_blocks] if c.multiview else []),
+                              scale, on_device=True)      # no device -> host read in the training step
     bufs = _AttnBufs(B, S, heads, dev)
-    sv.mv = None
-    if c.multiview:                                                                  # :273-348
-        if Nv % T:
-            raise ValueError(f"{Nv} video tokens cannot be split over {T} frames for the multiview blocks")
-        Pm = Nv // T
-        mv = _Saved()
-        mv.idx = _mv_index(b0, nv_, T, Nt, Pm, S, dev)
-        mv.Sm, mv.Bm = nv_ * (Nt + Pm), b0 * T
-        mv.R = mv.Bm * mv.Sm
-        mv.n_text = nv_ * Nt
-        wmv, bmv = model._mv_pointer_tables(dev)
-        mv.mod = ops.modulation_tables(temb, None, wmv, bmv, L, B, 1, E, 3 * D, mod_text)        # [L, B, 2, 3D]
-        mv.grp0 = ops.groups(S, Nt, 0)
+    mv = sv.mv = st.mv
+    if mv is not None:                                                               # :273-348
+        mv.Bm = sh.b0 * sh.T
         mv.bufs = _AttnBufs(mv.Bm, mv.Sm, heads, dev)
         # gate of (b f)-batch row groups {text, view 0, view 1, ...}: text rows of the attention output are dropped (zero gate)
-        mv.grp = ops.groups(mv.Sm, mv.n_text, Pm)
-        sv.mv = mv
+        mv.grp = ops.groups(mv.Sm, mv.n_text, sh.Nv // sh.T)
     # One transformer block (+ its multiview block) as a function of its input: the forward proper, and - under gradient
     # checkpointing - the recompute the backward asks for (the reference wraps every block in torch.utils.checkpoint,
     # cogvideox_control.py:867-899; enabled by config/traj_image_2b_multiview.yaml:33 and BASELINE configs[4]).  Everything else it
     # needs (modulation tables, row maps, RoPE tables, scratch) lives in `sv` / this closure for the lifetime of the step.
-    mv = sv.mv
-    rope_view = sv.rope_view
     def run_block(i, x):
         blk = model.transformer_blocks[i]
         mly = None
@@ -478,28 +311,9 @@ def forward_train(model, hidden_states, encoder_hidden_states, controls, timeste
     sv.recompute = recompute
     sv.lora = lora
     sv.x_last = x
-    gv = ops.groups(Nv, 0, per_group)
-    sv.vis, sv.vis2 = e(B * Nv, D), e(B * Nv, D)
-    ops.layernorm_modulate(x, sv.vis, model.norm_final.weight, model.norm_final.bias, None, None, 0, 0, gv, B, D, c.norm_eps,
-                           xmap=ops.rowmap(Nv, S, Nt))
-    no = model.norm_out
-    ops.layernorm_modulate(sv.vis, sv.vis2, no.norm.weight, no.norm.bias, modf[..., D:], modf[..., :D], G * 2 * D, 2 * D, gv, B,
-                           D, c.norm_eps)
-    fo = model.proj_out.weight.shape[0]
-    sv.fo_pad = (fo + 63) // 64 * 64
-    wo_, bo_ = model.proj_out.weight, model.proj_out.bias
-    if sv.fo_pad != fo:                       # CogVideoX1.5 (p_t = 2): 128 -> fits; tiny test configs: zero-padded columns
-        wo_ = torch.nn.functional.pad(wo_, (0, 0, 0, sv.fo_pad - fo)).contiguous()
-        bo_ = torch.nn.functional.pad(bo_, (0, sv.fo_pad - fo)).contiguous() if bo_ is not None else None
-    out_tok = e(B * Nv, sv.fo_pad)
-    ops.gemm(sv.vis2, wo_, bo_, out_tok, B * Nv, sv.fo_pad, D)
-    if sv.fo_pad != fo:
-        out_tok = out_tok[:, :fo].contiguous()
-    c_out = fo // (p * p * (pt or 1))
-    output = ops.unpatchify(out_tok, B, T, c_out, Hh, Ww, p, pt)
-    if nv_ > 1:                                                                      # :941
-        output = output.reshape(b0, nv_ * T, *output.shape[2:])
-    return output, is_mask, actions_recon, sv
+    sv.vis, sv.vis2 = e(B * sh.Nv, D), e(B * sh.Nv, D)
+    output, sv.fo_pad = stages.head(model, sh, x, sv.vis, sv.vis2, st.modf)
+    return output, st.is_action_mask, st.actions_recon, sv
 
 
 def _gelu_tanh_grad(u):
