@@ -754,6 +754,33 @@ int orv_lm_compose(const void* masks, int mask_bytes, int F, int n, int H, int W
                    const int* order, int m, const unsigned char* label_ids, const unsigned char* palette, unsigned* steps,
                    unsigned char* index, unsigned char* color, void* stream);
 
+/* -- Cascaded rollouts: the chunk boundary on the device -----------------------------------------------------------------------------------
+ * Replaces what the reference's cascade (orv/pipeline/evaluation_control_to_video.py:349-362) does on the host between two denoise loops:
+ * VideoProcessor.postprocess_video(..., 'pil') (an fp32 copy of the clip to the host, two numpy passes, PIL frames) and, for the frame
+ * handed to the next chunk, VideoProcessor.preprocess (PIL -> numpy -> tensor -> device).  The contract is DESIGN.md section 19.  No atomics,
+ * no LDS; every output value depends on one input value: bit-reproducible.  Every argument is checked before any launch, no device pointer
+ * is followed on the host, and every element a kernel can touch is checked to lie inside the extents given.
+ *
+ * The decoder's output to uint8 frames (replaces postprocess_video's 'pil' branch, evaluation_control_to_video.py:349): src is bf16
+ * (src_bytes = 2) or fp32 (4) [B, 3, F, H, W] with element strides src_stride[5] = (b, c, f, y, x) behind a pointer to element (0, 0, 0, 0,
+ * 0) with src_extent elements behind it.  Frames [f0, f1) of every clip are written to dst, uint8 [.., H, W, 3] frames of contiguous
+ * rows, frame f of clip b at byte b dst_stride_b + (dst_f0 + f - f0) dst_stride_f, with dst_extent bytes behind dst: a chunk's stitched
+ * range lands in the episode buffer directly.  Per value, in fp32 with one rounding per step: y = fl(fl(x / 2) + 0.5), clamped to
+ * [0, 1], u = rint_half_even(fl(y * 255)); +inf gives 255, -inf 0 and NaN 0 (numpy's cast of a NaN is platform-defined).  No fast-math.
+ * A lane owns 8 consecutive pixels of a row (three 16-byte plane loads for bf16, 24 output bytes as six dwords) where x is the unit
+ * stride, the three plane rows are 16-byte and the destination row 4-byte aligned; the last W % 8 pixels and every other row go pixel by
+ * pixel.  Traffic: 3 src_bytes + 3 bytes per pixel.  f0 == f1 launches nothing. */
+int orv_frames_quantize(const void* src, int src_bytes, long src_extent, const long* src_stride, int B, int H, int W, int f0, int f1,
+                        unsigned char* dst, long dst_extent, long dst_stride_b, long dst_stride_f, int dst_f0, void* stream);
+/* One uint8 frame per clip to the VAE encoder's input (replaces preprocess on the PIL frame videos[0][index] and the copy to the device,
+ * evaluation_control_to_video.py:361-362 and :317 into cogvideox_control.py:1366): src uint8 [B, F, H, W, 3] with byte strides
+ * src_stride[5] = (b, f, y, x, c) and src_extent bytes behind it; frame `frame` of every clip goes to out bf16 [B, 1, H, W, 8], contiguous
+ * and 16-byte aligned, channels 0-2 = table[u], channels 3-7 zero.  table is bf16 [256] on the device, built on the host with preprocess'
+ * own statements (level / 255 in fp32, 2 x - 1 in fp32, rounded to bf16), so the values equal the host path's by construction.  A lane owns
+ * a pixel: three bytes in, one 16-byte store. */
+int orv_frames_handoff(const unsigned char* src, long src_extent, const long* src_stride, int B, int F, int H, int W, int frame,
+                       const void* table, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,4 +34,10 @@ def __getattr__(name):
     if name in ("remove_statistical_outlier", "estimate_normals", "orient_normals_towards_camera_location", "preprocess_points", "nksr_inputs"):
         from . import pointcloud
         return getattr(pointcloud, name)
+    # cascaded long-video rollouts (orv_amd/rollout.py), resolved on first use likewise
+    # (`rollout` is the callable module itself, the one object that name ever holds: see the end of orv_amd/rollout.py)
+    if name in ("rollout", "plan_slices", "stitch_ranges"):
+        from importlib import import_module
+        module = import_module(".rollout", __name__)
+        return module if name == "rollout" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -169,6 +169,8 @@ SIGNATURES = {
     "orv_pc_orient": (c_int, [c_void_p, c_void_p, c_int] + [c_double] * 3 + [c_void_p, c_void_p]),
     "orv_lm_mask_stats": (c_int, [c_void_p] + [c_int] * 5 + [c_long, c_long, c_float, c_int] + [c_void_p] * 4),
     "orv_lm_compose": (c_int, [c_void_p] + [c_int] * 5 + [c_long, c_long, c_float, c_void_p, c_int] + [c_void_p] * 6),
+    "orv_frames_quantize": (c_int, [c_void_p, c_int, c_long, c_void_p] + [c_int] * 5 + [c_void_p, c_long, c_long, c_long, c_int, c_void_p]),
+    "orv_frames_handoff": (c_int, [c_void_p, c_long, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

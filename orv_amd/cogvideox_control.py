@@ -1183,6 +1183,14 @@ class CogVideoXPipelineOutput:
         self.frames = frames
 
 
+class ChannelsLastFrames:
+    """Marks a bf16 [B, 1, H, W, 8] tensor as reference frames already laid out for ``vae.encode_channels_last`` (what
+    ``orv_frames_handoff`` writes for a rollout's next chunk), so that ``prepare_latents`` encodes it as it is."""
+
+    def __init__(self, data):
+        self.data = data
+
+
 class CogVideoXImageToVideoPipelineTraj:
     """The reference's I2V pipeline (:1090-1489) with the call surface its entry points use
     (/root/reference/orv/pipeline/inference_control_to_video.py:71-146, evaluation_control_to_video.py:245-349):
@@ -1496,22 +1504,7 @@ class CogVideoXImageToVideoPipelineTraj:
     def _scale(self):
         return 1 / self.vae_scaling_factor_image if self.invert_scale_latents else self.vae_scaling_factor_image
 
-    def prepare_latents(self, image: torch.Tensor, batch_size: int = 1, num_channels_latents: int = 16,
-                        num_frames: int = 13, num_views: int = 1, height: int = 60, width: int = 90,
-                        dtype: Optional[torch.dtype] = None, device: Optional[torch.device] = None,
-                        generator: Optional[torch.Generator] = None, latents: Optional[torch.Tensor] = None):
-        if isinstance(generator, list) and len(generator) != batch_size:
-            raise ValueError(
-                f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
-                f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
-        pt = self.transformer.config.patch_size_t
-        t_lat = (num_frames - 1) // self.vae_scale_factor_temporal + 1
-        shape = (batch_size, num_views * t_lat, num_channels_latents, height // self.vae_scale_factor_spatial,
-                 width // self.vae_scale_factor_spatial)
-        if pt is not None:
-            shape = shape[:1] + (shape[1] + shape[1] % pt,) + shape[2:]
-        if image.ndim not in (4, 5):
-            raise RuntimeError(f'Invalid dimensions of image input: {image.shape=}')
+    def _image_latents(self, image, batch_size, num_channels_latents, num_views, dtype, device, generator):
         ch = image.size(1)
         image = image.to(device=device, dtype=dtype)
         if image.ndim == 4:
@@ -1536,6 +1529,36 @@ class CogVideoXImageToVideoPipelineTraj:
             image_latents = (self._scale() * image).permute(0, 2, 1, 3, 4)
         else:
             raise RuntimeError(f'Invalid input channels {image.shape=} while {num_channels_latents=}!')
+        return image_latents
+
+    def prepare_latents(self, image: torch.Tensor, batch_size: int = 1, num_channels_latents: int = 16,
+                        num_frames: int = 13, num_views: int = 1, height: int = 60, width: int = 90,
+                        dtype: Optional[torch.dtype] = None, device: Optional[torch.device] = None,
+                        generator: Optional[torch.Generator] = None, latents: Optional[torch.Tensor] = None):
+        if isinstance(generator, list) and len(generator) != batch_size:
+            raise ValueError(
+                f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
+        pt = self.transformer.config.patch_size_t
+        t_lat = (num_frames - 1) // self.vae_scale_factor_temporal + 1
+        shape = (batch_size, num_views * t_lat, num_channels_latents, height // self.vae_scale_factor_spatial,
+                 width // self.vae_scale_factor_spatial)
+        if pt is not None:
+            shape = shape[:1] + (shape[1] + shape[1] % pt,) + shape[2:]
+        if isinstance(image, ChannelsLastFrames):
+            from .vae import DiagonalGaussianDistribution
+            # reference frames a rollout handed over on the device, already in the encoder's layout [b, f, H, W, 8]: the same moments as
+            # vae.encode gives on the same pixels (its own first step is this layout), sampled clip by clip as below
+            h = image.data
+            if num_views != 1 or h.shape[0] != batch_size:
+                raise RuntimeError(f'Invalid channels-last image input: {tuple(h.shape)=} for {batch_size=} and {num_views=}!')
+            gens = generator if isinstance(generator, list) else [generator] * batch_size
+            lats = [DiagonalGaussianDistribution(self.vae.encode_channels_last(h[i:i + 1], dtype=dtype)).sample(gens[i]) for i in range(batch_size)]
+            image_latents = self._scale() * torch.cat(lats, dim=0).to(dtype).permute(0, 2, 1, 3, 4)       # [b, f, C, h, w]
+        elif image.ndim not in (4, 5):
+            raise RuntimeError(f'Invalid dimensions of image input: {image.shape=}')
+        else:
+            image_latents = self._image_latents(image, batch_size, num_channels_latents, num_views, dtype, device, generator)
         b, vf = image_latents.shape[:2]
         image_latents = image_latents.reshape(b, num_views, vf // num_views, *image_latents.shape[2:])
         f_img = image_latents.size(2)
@@ -1562,6 +1585,30 @@ class CogVideoXImageToVideoPipelineTraj:
                  attention_kwargs=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 226,
                  controls_or_guidances: Dict[str, torch.Tensor] = {}):
+        call = self._prepare_call(image, prompt, negative_prompt, height, width, num_views, num_frames, num_inference_steps, timesteps,
+                                  guidance_scale, use_dynamic_cfg, num_videos_per_prompt, eta, generator, latents, prompt_embeds,
+                                  negative_prompt_embeds, output_type, return_dict, attention_kwargs, callback_on_step_end,
+                                  callback_on_step_end_tensor_inputs, max_sequence_length, controls_or_guidances)
+        image = self.video_processor.preprocess(image, height=height, width=width).to(device=call.device, dtype=call.dtype)   # :1366
+        video = self._generate(image, call, decode=output_type != "latent")
+        if output_type != "latent":                                                  # :1477-1479
+            video = self.video_processor.postprocess_video(video=video, output_type=output_type)
+        self.maybe_free_model_hooks()
+        if not return_dict:
+            return (video,)
+        return CogVideoXPipelineOutput(frames=video)
+
+    @torch.no_grad()
+    def _prepare_call(self, image, prompt=None, negative_prompt=None, height: Optional[int] = None,
+                 width: Optional[int] = None, num_views: int = 1, num_frames: int = 49, num_inference_steps: int = 50,
+                 timesteps: Optional[List[int]] = None, guidance_scale: float = 6, use_dynamic_cfg: bool = False,
+                 num_videos_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
+                 negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
+                 attention_kwargs=None, callback_on_step_end=None,
+                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 226,
+                 controls_or_guidances: Dict[str, torch.Tensor] = {}):
+        """The part of ``__call__`` in front of ``video_processor.preprocess`` (:1261-1364): input checks, prompt embeddings, timesteps,
+        the frame count's padding and the occupancy controls.  -> the call's state, which ``_generate`` consumes."""
         tr, sched = self.transformer, self.scheduler
         self.check_inputs(image, prompt, height, width, negative_prompt, callback_on_step_end_tensor_inputs, prompt_embeds,
                           negative_prompt_embeds)
@@ -1602,8 +1649,27 @@ class CogVideoXImageToVideoPipelineTraj:
                 eps = torch.randn((cm.shape[0], latent_channels) + tuple(cm.shape[2:]), device=device, dtype=dtype)
                 lat = ops.gaussian_sample(cm, eps.float(), self._scale())
                 controls[key] = torch.cat([lat, lat], dim=2)
-        image = self.video_processor.preprocess(image, height=height, width=width).to(device=device, dtype=dtype)   # :1366
-        latents, image_latents = self.prepare_latents(image, batch_size * num_videos_per_prompt, latent_channels,
+        from types import SimpleNamespace
+        return SimpleNamespace(device=device, dtype=dtype, do_cfg=do_cfg, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                               batch_size=batch_size * num_videos_per_prompt, ts_host=ts_host, num_inference_steps=num_inference_steps,
+                               latent_channels=latent_channels, num_frames=num_frames, num_views=num_views, height=height, width=width,
+                               controls=controls, generator=generator, latents=latents, guidance_scale=guidance_scale,
+                               use_dynamic_cfg=use_dynamic_cfg, attention_kwargs=attention_kwargs, callback_on_step_end=callback_on_step_end,
+                               callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs)
+
+    @torch.no_grad()
+    def _generate(self, image, call, decode: bool = True):
+        """The part of ``__call__`` behind ``video_processor.preprocess`` (:1367-1479): ``image`` is the preprocessed reference image on the
+        device (RGB in [-1, 1], latents or moments; ``ChannelsLastFrames`` for a frame handed over on the device) -> the decoded
+        video [B, 3, F, H, W] on the device, or with ``decode=False`` the latents.  The generator is consumed in this order: image
+        latents, initial noise, DPM noise."""
+        tr, sched = self.transformer, self.scheduler
+        device, dtype, do_cfg, prompt_embeds, negative_prompt_embeds = call.device, call.dtype, call.do_cfg, call.prompt_embeds, call.negative_prompt_embeds
+        ts_host, num_inference_steps, latent_channels, num_frames, num_views = call.ts_host, call.num_inference_steps, call.latent_channels, call.num_frames, call.num_views
+        height, width, controls, generator, latents, guidance_scale = call.height, call.width, call.controls, call.generator, call.latents, call.guidance_scale
+        use_dynamic_cfg, attention_kwargs, callback_on_step_end = call.use_dynamic_cfg, call.attention_kwargs, call.callback_on_step_end
+        callback_on_step_end_tensor_inputs, pt = call.callback_on_step_end_tensor_inputs, tr.config.patch_size_t
+        latents, image_latents = self.prepare_latents(image, call.batch_size, latent_channels,
                                                       num_frames, num_views, height, width, dtype, device, generator,
                                                       latents)
         image_rotary_emb = None
@@ -1650,14 +1716,13 @@ class CogVideoXImageToVideoPipelineTraj:
                 prompt_embeds = cb.pop("prompt_embeds", prompt_embeds)
         b, vf = latents.shape[:2]
         latents = latents.reshape(b * num_views, vf // num_views, *latents.shape[2:])
-        video = latents
-        if output_type != "latent":                                                  # :1477-1479
-            video = self.decode_latents(latents)
-            video = self.video_processor.postprocess_video(video=video, output_type=output_type)
-        self.maybe_free_model_hooks()
-        if not return_dict:
-            return (video,)
-        return CogVideoXPipelineOutput(frames=video)
+        return self.decode_latents(latents) if decode else latents
+
+    def rollout(self, image, plan, controls_for_slice, **kw):
+        """A cascaded long-video rollout (``orv_amd.rollout.rollout``): one call of this pipeline per slice of ``plan``, the frame handed
+        from chunk to chunk and the stitched uint8 episode kept on the device."""
+        from .rollout import rollout
+        return rollout(self, image, plan, controls_for_slice, **kw)
 
 
 def _retrieve_latents(encoder_output, generator=None):

@@ -1262,3 +1262,63 @@ def lm_compose(masks, order, label_ids, palette, threshold=0.0):
                                    (ctypes.c_ubyte * max(n, 1))(*label_ids), (ctypes.c_ubyte * 180)(*palette), _p(steps), _p(index), _p(color),
                                    _stream()), "orv_lm_compose")
     return index, color
+
+
+# ---- cascaded rollouts: the chunk boundary (csrc/frames.hip) ----
+def _behind(t):
+    """Elements of ``t``'s storage from its first element on: the extent the kernels' bound checks are held to."""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def frames_quantize(video, f0: int = 0, f1: Optional[int] = None, out=None, dst_f0: int = 0):
+    """video bf16 / fp32 [B, 3, F, H, W] (a view of any strides: the decoder's output) -> frames [f0, f1) of every clip as uint8
+    [B, f1 - f0, H, W, 3], by ``postprocess_video``'s 'pil' arithmetic (x / 2 + 0.5, clamp, * 255, round half to even; NaN -> 0).  With
+    ``out`` (uint8 [B, N, H, W, 3] whose frames are contiguous; batch and frame strides are free) they are written at frame offset
+    ``dst_f0`` of it and ``out`` is returned."""
+    if not isinstance(video, torch.Tensor) or video.dtype not in (BF16, torch.float32):
+        raise RuntimeError(f"orv_amd.ops: `video` must be a torch.bfloat16 or torch.float32 tensor (got {getattr(video, 'dtype', type(video).__name__)})")
+    _need(video, video.dtype, "video")
+    if video.dim() != 5 or video.shape[1] != 3 or 0 in video.shape:
+        raise ValueError(f"frames_quantize: video must be [B, 3, F, H, W] and not empty (got {tuple(video.shape)})")
+    B, _, F, H, W = video.shape
+    f1 = F if f1 is None else int(f1)
+    f0, dst_f0 = int(f0), int(dst_f0)
+    if not 0 <= f0 <= f1 <= F:
+        raise ValueError(f"frames_quantize: frames [{f0}, {f1}) of a clip of {F}; supported: 0 <= f0 <= f1 <= F")
+    if out is None:
+        if dst_f0:
+            raise ValueError("frames_quantize: dst_f0 needs `out`")
+        out = torch.empty(B, f1 - f0, H, W, 3, dtype=torch.uint8, device=video.device)
+    _need(out, torch.uint8, "out")
+    _same_device((video, "video"), (out, "out"))
+    if out.dim() != 5 or out.shape[0] != B or tuple(out.shape[2:]) != (H, W, 3):
+        raise ValueError(f"frames_quantize: out must be [B = {B}, N, H = {H}, W = {W}, 3] (got {tuple(out.shape)})")
+    if dst_f0 < 0 or dst_f0 + (f1 - f0) > out.shape[1]:
+        raise ValueError(f"frames_quantize: {f1 - f0} frames at frame offset {dst_f0} of a destination of {out.shape[1]} frames")
+    if out.numel() and tuple(out.stride()[2:]) != (W * 3, 3, 1):
+        raise ValueError(f"frames_quantize: the [H, W, 3] frames of `out` must be contiguous (strides {out.stride()})")
+    if f1 > f0:
+        with _timed(("frames_quantize", video.element_size(), B, f1 - f0, H, W)):
+            check(lib().orv_frames_quantize(_p(video), video.element_size(), _behind(video), (ctypes.c_long * 5)(*video.stride()), B, H, W, f0, f1,
+                                            _p(out), _behind(out), out.stride(0), out.stride(1), dst_f0, _stream()), "orv_frames_quantize")
+    return out
+
+
+def frames_handoff(frames, index: int, table):
+    """frames uint8 [B, F, H, W, 3] (a view of any strides), ``table`` bf16 [256] on the same device -> frame ``index`` of every clip as
+    the bf16 channels-last tensor [B, 1, H, W, 8] that ``vae.encode_channels_last`` reads: channels 0-2 = table[level], 3-7 zero."""
+    _need(frames, torch.uint8, "frames"), _need(table, BF16, "table")
+    _same_device((frames, "frames"), (table, "table"))
+    if frames.dim() != 5 or frames.shape[4] != 3 or 0 in frames.shape:
+        raise ValueError(f"frames_handoff: frames must be [B, F, H, W, 3] and not empty (got {tuple(frames.shape)})")
+    if tuple(table.shape) != (256,) or not table.is_contiguous():
+        raise ValueError(f"frames_handoff: table must be a contiguous bf16 [256] (got {tuple(table.shape)})")
+    B, F, H, W, _ = frames.shape
+    index = int(index)
+    if not 0 <= index < F:
+        raise ValueError(f"frames_handoff: frame {index} of clips of {F} frames")
+    out = torch.empty(B, 1, H, W, 8, dtype=BF16, device=frames.device)
+    with _timed(("frames_handoff", B, H, W)):
+        check(lib().orv_frames_handoff(_p(frames), _behind(frames), (ctypes.c_long * 5)(*frames.stride()), B, F, H, W, index, _p(table), _p(out),
+                                       _stream()), "orv_frames_handoff")
+    return out

@@ -181,6 +181,8 @@ class CogVideoXDPMScheduler(_CogVideoXScheduler):
 
 def _randn_like(sample, generator):
     dev = sample.device
+    if isinstance(generator, list):          # one generator per batch element, as diffusers' randn_tensor takes them
+        return torch.cat([_randn_like(sample[i:i + 1], g) for i, g in enumerate(generator)], dim=0)
     if generator is not None and generator.device.type == "cpu" and dev.type != "cpu":
         n = torch.randn(sample.shape, generator=generator, device="cpu", dtype=sample.dtype).to(dev)
     else:
