@@ -57,17 +57,6 @@ __device__ __forceinline__ bool attn_guard_selects(const AttnArgs& p, bool stati
 }
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-// -DORV_SEG_TRACE (tools/attn_seg_trace.sh): per-wave time in the matrix segment, at the barrier behind it, in the vector segment and
-// at the barrier behind that, summed over the tiles (s_memrealtime ticks of 10 ns), written through the lse pointer
-#ifdef ORV_SEG_TRACE
-#define SEG_T(I) { const unsigned long long now_ = wall_clock64(); if ((I) > 0) seg_acc[(I) - 1] += now_ - seg_last; seg_last = now_; }
-#define SEG_DECL unsigned long long seg_acc[4] = {0, 0, 0, 0}, seg_last = 0;
-#define SEG_DUMP if (p.lse && lane == 0) { unsigned long long* tr_ = (unsigned long long*)p.lse + ((long)blockIdx.x * 8 + wave) * 4; for (int i_ = 0; i_ < 4; ++i_) tr_[i_] = seg_acc[i_]; }
-#else
-#define SEG_T(I)
-#define SEG_DECL
-#define SEG_DUMP
-#endif
 // max over this lane and lane ^ 32 without an LDS round trip
 __device__ __forceinline__ float max_with_partner_half(float v) {
     const unsigned u = __float_as_uint(v);
@@ -457,9 +446,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
     const int D = p.H * 64;
     const long row0 = (long)b * p.S;
     const bool active = q0 < p.S;          // a wave whose 32 query rows all lie past S only stages tiles and meets the barriers
-#ifdef ORV_PP_TRACE
-    const unsigned long long trace_t0 = wall_clock64();     // tools/attn_trace.sh: workgroup start / end on the 100 MHz clock
-#endif
 
     bf16x8 qf[4];
     {
@@ -527,9 +513,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
     // score registers are dead (32 free for V^T fragments), while QK^T runs P is (16 free for K fragments): peak stays under 128.
 #define PP_FENCE() __builtin_amdgcn_sched_barrier(0);
     auto seg_x = [&](int t, auto stage_k) {
-#ifndef ORV_PP_NOPRIO
         __builtin_amdgcn_s_setprio(1);      // matrix segment first on the SIMD (+1-3 %, same-process A/B)
-#endif
         const char* sK = smem + (t % PP_SLOTS) * TILE_BYTES + row_off;
         auto kread = [&](int kb, int ks) { return *(const bf16x8*)(sK + kb * 4096 + (((ks * 2 + hi) ^ sw) * 16)); };
         bf16x8 k0, k1, k2, k3;
@@ -589,9 +573,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
             sT[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k3, qf[3], sT[1], 0, 0, 0);
             PP_FENCE()
         }
-#ifndef ORV_PP_NOPRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
     };
     // vector segment: softmax of tile t -> packed P_t
     auto seg_y = [&](int t) {
@@ -607,18 +589,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
         }
         float psum = 0.f;
         if constexpr (STATIC) {
-#ifdef ORV_PP_PSUM4
-            float ps4[4] = {0.f, 0.f, 0.f, 0.f};      // four independent chains instead of one 32-deep dependent add chain
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float pv = fast_exp2(sT[kb][r]);
-                    sT[kb][r] = pv;
-                    ps4[r & 3] += pv;
-                }
-            psum = (ps4[0] + ps4[1]) + (ps4[2] + ps4[3]);
-#else
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -627,7 +597,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
                     sT[kb][r] = pv;
                     psum += pv;
                 }
-#endif
         } else {
             float tmax = sT[0][0];
 #pragma unroll
@@ -673,20 +642,14 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     PP_BAR()
     const bool act = __builtin_amdgcn_readfirstlane((int)active) != 0;       // provably wave-uniform: real branches, no exec masking
-    SEG_DECL
     if (grp == 0) {
         if (act) {
             for (int t = t_lo; t < t_hi; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() { if (t + 1 < t_hi) stage(t + 1); });
-                SEG_T(1)
                 PP_BAR()
-                SEG_T(2)
                 seg_y(t);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                SEG_T(3)   // K_{t+1} landed (this wave's pieces); visible after the barrier
                 PP_BAR()
-                SEG_T(4)
             }
             seg_x(t_hi, [&]() {});
         } else {
@@ -702,18 +665,13 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
         PP_BAR()
         if (act) {
             for (int t = t_lo; t < t_hi; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() {});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                SEG_T(1)   // V_t landed (issued in Y_{t-1} / the prologue)
                 PP_BAR()
-                SEG_T(2)
                 if (t + 1 < t_hi) stage(t + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 seg_y(t);
-                SEG_T(3)
                 PP_BAR()
-                SEG_T(4)
             }
             seg_x(t_hi, [&]() {});
         } else {
@@ -783,21 +741,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
         }
     }
     const float inv = 1.0f / l_tot;
-    SEG_DUMP
-#ifdef ORV_PP_TRACE
-    // timeline build only (never the product library): (start, end, HW_ID | XCC_ID << 32, item) per workgroup through the lse pointer
-    if (p.lse && tid == 0) {
-        unsigned long long* tr = (unsigned long long*)p.lse + (long)blockIdx.x * 4;
-        tr[0] = trace_t0; tr[1] = wall_clock64();
-        tr[2] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);
-        tr[3] = (unsigned long long)item;
-    }
-    const bool write_lse = false;
-#elif defined(ORV_SEG_TRACE)
-    const bool write_lse = false;
-#else
-    const bool write_lse = true;
-#endif
     if (q < p.S) {
         // lane holds d = 32 db + 8 qd + 4 hi + (0..3) of row q: groups qd = 2 u (lower half-wave) and 2 u + 1 (upper) are exchanged
         // so that every lane stores ONE aligned 16-byte piece: lower -> d 32 db + 16 u + 0..7, upper -> + 8..15
@@ -820,7 +763,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pp_kernel(const AttnArgs p) {
                 if (!SPLIT && p.out_packed) *(uint4*)(pblk + db * 1024 + u * 512) = make_uint4(a0, a1, b0, b1);
                 else *(uint4*)(op + db * 32 + u * 16) = make_uint4(a0, a1, b0, b1);
             }
-        if (write_lse && p.lse && hi == 0)
+        if (p.lse && hi == 0)
             p.lse[((long)b * p.H + h) * p.S + q] = (STATIC ? __log2f(l_tot) : m_run + __log2f(l_tot)) * 0.6931471805599453f;
     }
 }
@@ -1090,11 +1033,6 @@ __device__ __forceinline__ void m16_glds16(const char* sbase, unsigned voff, con
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(su), "s"(d) : "memory");
 }
-__device__ __forceinline__ float m16_sum_groups(float v) {          // sum over the four lane groups (lanes c, c + 16, c + 32, c + 48)
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * PP_SLOTS * TILE_BYTES];   // K slots | V slots
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1108,9 +1046,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
     const int D = p.H * 64;
     const long row0 = (long)b * p.S;
     const bool active = q0 < p.S;
-#ifdef ORV_PP_TRACE
-    const unsigned long long trace_t0 = wall_clock64();
-#endif
 
     bf16x8 qf[2][2];                     // [query block][k-step]: d = 32 ks + 8 g .. + 7 of query row q0 + 16 qb + c
 #pragma unroll
@@ -1164,10 +1099,8 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) pf[i][j].u[e] = 0u;
-    float l_run[2] = {0.f, 0.f};
-#ifndef ORV_M16_VALUSUM
     // Row sums on the matrix pipe: l^T (qb) += ones[16 x 32] . P^T (key step s, qb) - one extra MFMA per key step and query block
-    // (+12.5 % MFMAs) instead of 32 v_add_f32 per tile.  The per-segment timing (tools/attn_seg_trace.sh) shows why: the vector
+    // (+12.5 % MFMAs) instead of 32 v_add_f32 per tile.  The per-segment timing (profiles/r3_attention_pingpong.txt) shows why: the vector
     // segment, not the matrix segment, is the long pole - the four waves of a SIMD need 4 x (32 quarter-rate v_exp_f32 + ~65 other
     // VALU instructions) = ~3100 VALU cycles per tile against 2048 MFMA cycles.  Every row of the product carries the sum, so
     // register 0 of any lane is the row sum of its query: no cross-lane reduction at the end.
@@ -1176,9 +1109,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
 #pragma unroll
     for (int e = 0; e < 4; ++e) ones.u[e] = 0x3f803f80u;
 #define M16_LSUM(S_) { lT[0] = M16_MFMA(ones.v, pf[S_][0].v, lT[0]); lT[1] = M16_MFMA(ones.v, pf[S_][1].v, lT[1]); }
-#else
-#define M16_LSUM(S_)
-#endif
     // K fragment of (kbk, ks): row 16 kbk + c, 16-byte chunk 4 ks + g, swizzled by (row >> 1) & 7 = (c >> 1) & 7
     const int k_row = c * 128, k_sw = (c >> 1) & 7;
     // V^T fragment pieces: lane (c, g) addresses key 4 g + (c >> 2) (+ 32 s + 16 half) and d 16 db + 4 (c & 3); segment db ^ fz
@@ -1189,26 +1119,16 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
     __builtin_amdgcn_s_barrier();                                                                 \
     __builtin_amdgcn_sched_barrier(0);
 #define M16_FENCE() __builtin_amdgcn_sched_barrier(0);
-#ifdef ORV_M16_ABL_NOMFMA
-#define M16_MFMA(A, B, C) (C)
-#else
 #define M16_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
-#endif
     auto seg_x = [&](int t, auto stage_k) {
         __builtin_amdgcn_s_setprio(1);
         const char* sK = smem + (t % PP_SLOTS) * TILE_BYTES + k_row;
         auto kread = [&](int kbk, int ks) {
-#ifdef ORV_M16_ABL_NOK
-            return qf[kbk & 1][ks];
-#endif
             return *(const bf16x8*)(sK + kbk * 2048 + (((4 * ks + g) ^ k_sw) * 16)); };
         bf16x8 ka, kb_, kc, kd, ke, kf, kg, kh;          // K fragments: (key block 0..3, k-step 0) | (key block 0..3, k-step 1)
         if (t > 0) {
             const char* sV = smem + PP_SLOTS * TILE_BYTES + ((t - 1) % PP_SLOTS) * TILE_BYTES + v_base;
             auto vread = [&](int db, int s_) {
-#ifdef ORV_M16_ABL_NOV
-                return qf[db & 1][s_];
-#endif
                 const char* a = sV + s_ * 4096 + ((db ^ v_fz) * 32);
                 return tr_read_pair(a, a + 2048);
             };
@@ -1273,22 +1193,13 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
                 for (int e = 0; e < 4; ++e)
                     if (kv0 + 16 * kbk + e >= p.S) { sT[kbk][0][e] = -INFINITY; sT[kbk][1][e] = -INFINITY; }
         }
-        float ps0 = 0.f, ps1 = 0.f;
 #pragma unroll
         for (int kbk = 0; kbk < 4; ++kbk)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-#ifdef ORV_M16_ABL_NOEXP
-                const float a = sT[kbk][0][e], b_ = sT[kbk][1][e];
-#else
-                const float a = fast_exp2(sT[kbk][0][e]), b_ = fast_exp2(sT[kbk][1][e]);
-#endif
-                sT[kbk][0][e] = a; sT[kbk][1][e] = b_;
-#ifdef ORV_M16_VALUSUM
-                ps0 += a; ps1 += b_;
-#endif
+                sT[kbk][0][e] = fast_exp2(sT[kbk][0][e]);
+                sT[kbk][1][e] = fast_exp2(sT[kbk][1][e]);
             }
-        l_run[0] += ps0; l_run[1] += ps1;
 #pragma unroll
         for (int s_ = 0; s_ < 2; ++s_)
 #pragma unroll
@@ -1304,20 +1215,14 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     M16_BAR()
     const bool act = __builtin_amdgcn_readfirstlane((int)active) != 0;
-    SEG_DECL
     if (grp == 0) {
         if (act) {
             for (int t = 0; t < nt; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() { if (t + 1 < nt) stage(t + 1); });
-                SEG_T(1)
                 M16_BAR()
-                SEG_T(2)
                 seg_y(t);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                SEG_T(3)
                 M16_BAR()
-                SEG_T(4)
             }
             seg_x(nt, [&]() {});
         } else {
@@ -1333,18 +1238,13 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
         M16_BAR()
         if (act) {
             for (int t = 0; t < nt; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() {});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                SEG_T(1)
                 M16_BAR()
-                SEG_T(2)
                 if (t + 1 < nt) stage(t + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 seg_y(t);
-                SEG_T(3)
                 M16_BAR()
-                SEG_T(4)
             }
             seg_x(nt, [&]() {});
         } else {
@@ -1360,24 +1260,11 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
 #undef M16_FENCE
 #undef M16_MFMA
 
-    SEG_DUMP
-#ifdef ORV_PP_TRACE
-    if (p.lse && tid == 0) {
-        unsigned long long* tr = (unsigned long long*)p.lse + (long)blockIdx.x * 4;
-        tr[0] = trace_t0; tr[1] = wall_clock64();
-        tr[2] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);
-        tr[3] = (unsigned long long)item;
-    }
-#endif
     // epilogue: lane (c, g) holds O^T[16 db + 4 g + e][query (qb, c)]; an even group keeps its d quad of db = 0 / 2 and takes the odd
     // partner's (lane ^ 16), the odd group the other way round for db = 1 / 3: every lane stores 8 consecutive d = 16 bytes
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
-#ifdef ORV_M16_VALUSUM
-        const float l_tot = m16_sum_groups(l_run[qb]);
-#else
         const float l_tot = lT[qb][0];
-#endif
         const float inv = 1.0f / l_tot;
         const int q = q0 + 16 * qb + c;
         bf16_t* op = p.out + (row0 + min(q, p.S - 1)) * p.ld_out + h * 64;
@@ -1398,9 +1285,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_m16_kernel(const AttnArgs p) 
                 } else *(uint4*)(op + d0) = make_uint4(x0, x1, y0, y1);
             }
         }
-#if !defined(ORV_SEG_TRACE) && !defined(ORV_PP_TRACE)
         if (p.lse && g == 0 && q < p.S) p.lse[((long)b * p.H + h) * p.S + q] = __log2f(l_tot) * 0.6931471805599453f;
-#endif
     }
 }
 

@@ -75,19 +75,6 @@ __global__ __launch_bounds__(256) void bwd_prep_kernel(const bf16_t* __restrict_
     }
 }
 
-// -DORV_SEG_TRACE (tools/attn_bwd_seg_trace.sh): per-wave time in the matrix segment, at the barrier behind it, in the vector segment
-// and at the barrier behind that, summed over the tiles (s_memrealtime ticks of 10 ns); the buffer is handed over by
-// orv_debug_attn_bwd_trace(), which exists in such builds only
-#ifdef ORV_SEG_TRACE
-__device__ unsigned long long* g_bwd_trace = nullptr;
-#define SEG_T(I) { const unsigned long long now_ = wall_clock64(); if ((I) > 0) seg_acc[(I) - 1] += now_ - seg_last; seg_last = now_; }
-#define SEG_DECL unsigned long long seg_acc[4] = {0, 0, 0, 0}, seg_last = 0;
-#define SEG_DUMP(K) if (g_bwd_trace && lane == 0) { unsigned long long* tr_ = g_bwd_trace + ((long)(K) * gridDim.x * 8 + (long)blockIdx.x * 8 + wave) * 4; for (int i_ = 0; i_ < 4; ++i_) tr_[i_] = seg_acc[i_]; }
-#else
-#define SEG_T(I)
-#define SEG_DECL
-#define SEG_DUMP(K)
-#endif
 struct BwdArgs {
     const bf16_t* qkv; long ld;      // q' | k | v (after orv_qkv_prep)
     const bf16_t* qT; const bf16_t* kT; const bf16_t* doT;   // [B,H,64,s_pad]
@@ -398,9 +385,6 @@ __device__ __forceinline__ void glds4_sv(const void* sbase, unsigned voff, const
 __device__ __forceinline__ int swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bf16x8 tr_pair(const char* a, const char* b) {
-#ifdef ORV_BW_ABL_NOTR
-    bf16x8 z; asm volatile("" : "=v"(z)); return z;
-#endif
     const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)a);
     const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)b);
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -410,11 +394,7 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* a, const char* b) {
     __builtin_amdgcn_s_barrier();                                                                 \
     __builtin_amdgcn_sched_barrier(0);
 #define BW_FENCE() __builtin_amdgcn_sched_barrier(0);
-#ifdef ORV_BW_ABL_NOMFMA
-#define BW_MFMA(A_, B_, C_) ([&]() { asm volatile("" ::"v"(A_), "v"(B_)); return C_; }())
-#else
 #define BW_MFMA(A_, B_, C_) __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, C_, 0, 0, 0)
-#endif
 // per-lane byte offsets of the transposing reads into a swizzled [64 rows][64 d] tile: contraction rows kk * 16 + half * 8 + 4 hi +
 // (r16 >> 2), logical bytes db * 64 + g16 * 32 + (r16 & 3) * 8 (4 consecutive d); + kk * 2048 is an immediate
 __device__ __forceinline__ int tr_off(int lane, int db, int half) {
@@ -482,9 +462,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_pp_kernel(const BwdArgs p)
     char* const sdst = smem + (grp == 0 ? 0 : 4 * TILE) + wq * 2048;
     auto stage = [&](int t) {
         if (t >= nt) return;
-#ifdef ORV_BW_ABL_NODMA
-        if (t > 1) return;
-#endif
         char* const d = sdst + (grp == 0 ? t & 3 : t & 1) * TILE;
         if (__builtin_expect(ragged && t == nt - 1, 0)) {
             glds16_asm(src_of(0, t), d);
@@ -526,9 +503,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_pp_kernel(const BwdArgs p)
         const char* sK = smem + (t & 3) * TILE + row_off;
         const char* sV = smem + 4 * TILE + (t & 1) * TILE + row_off;
         auto rd = [&](const char* base, int kb, int ks) {
-#ifdef ORV_BW_ABL_NOB128
-            bf16x8 z; asm volatile("" : "=v"(z)); return z;
-#endif
             return *(const bf16x8*)(base + kb * 4096 + (((ks * 2 + hi) ^ sw) * 16)); };
         bf16x8 ka0, va0, ka1, va1, kb0, vb0, kb1, vb1;
         if (t < nt) { ka0 = rd(sK, 0, 0); va0 = rd(sV, 0, 0); ka1 = rd(sK, 0, 1); va1 = rd(sV, 0, 1); }   // first score fragments: in flight under the gradient MFMAs
@@ -571,13 +545,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_pp_kernel(const BwdArgs p)
     auto seg_y = [&](int t) {
         prefetch_g(t);
         BW_FENCE()
-#ifdef ORV_BW_ABL_NOY
-        asm volatile("" ::"v"(sT[0]), "v"(sT[1]), "v"(dP[0]), "v"(dP[1]));
-        return;
-#endif
         // keys past S (ragged last tile only): score -> -inf, P = 0.  A separate, uniform branch: folded into the element loop the
         // compare + select pair (and the s_nop between them) ran for EVERY element of EVERY tile - 190 instead of 64 VALU
-        // instructions per tile in a segment that has the SIMD's VALU port to itself (tools/attn_bwd_seg_trace.py: 860-1070 ns)
+        // instructions per tile in a segment that has the SIMD's VALU port to itself (profiles/r3_attention_bwd_pingpong.txt: 860-1070 ns)
         if (__builtin_expect(ragged && t == nt - 1, 0)) {
             int kv0 = t * 64 + 4 * hi;
             asm volatile("" : "+v"(kv0));
@@ -603,22 +573,16 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_pp_kernel(const BwdArgs p)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     BW_BAR()
     const bool act = __builtin_amdgcn_readfirstlane((int)(q0 < p.S)) != 0;
-    SEG_DECL
     if (grp == 0) {
         if (act) {
             for (int t = 0; t < nt; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() {});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // K_{t+1} landed (issued in Y_{t-1} / the prologue)
-                SEG_T(1)
                 BW_BAR()
-                SEG_T(2)
                 stage(t + 2);                                    // K_{t+2} -> slot of K_{t-2} (last read in the partners' X_{t-1}, two intervals ago)
                 BW_FENCE()
                 seg_y(t);
-                SEG_T(3)
                 BW_BAR()
-                SEG_T(4)
             }
             seg_x(nt, [&]() {});
         } else {
@@ -634,18 +598,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_pp_kernel(const BwdArgs p)
         BW_BAR()
         if (act) {
             for (int t = 0; t < nt; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() {});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // V_{t+1} landed (issued in Y_{t-1} / the prologue)
-                SEG_T(1)
                 BW_BAR()
-                SEG_T(2)
                 stage(t + 2);                                    // V_{t+2} -> slot of V_t (last read in this half's X_t)
                 BW_FENCE()
                 seg_y(t);
-                SEG_T(3)
                 BW_BAR()
-                SEG_T(4)
             }
             seg_x(nt, [&]() {});
         } else {
@@ -657,7 +616,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_pp_kernel(const BwdArgs p)
             }
         }
     }
-    SEG_DUMP(0)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int q = q0 + l31;
     if (q < p.S) store_row16(p.dqkv + (row0 + q) * p.ld_dqkv + h * 64 + hi * 8, dq, p.scale);
@@ -668,26 +626,15 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_pp_kernel(const BwdArgs p)
 // (16 MFMAs, ds_read_b128; -lse / -delta of the tile's 64 query rows enter through the accumulator init, from LDS) } ;
 // Y_t = { P = exp2(S), dS = P dP, bf16 pack of both }.  Q' tiles (+ the lse vector): four slots, staged by waves 0-3; dO tiles (+ the delta
 // vector): three slots, staged by waves 4-7; both two tiles ahead, from the vector segment.
-// Shared fragment buffer (round 6; -DORV_BW_NO_FRAGBUF builds the round-5 form for A/B): the transposed fragments (dO^T, Q'^T) of k-steps 1-3 are the SAME for all eight waves, and every wave
+// Shared fragment buffer (round 6): the transposed fragments (dO^T, Q'^T) of k-steps 1-3 are the SAME for all eight waves, and every wave
 // fetched them with 24 ds_read_b64_tr_b16 in its matrix segment - the segment that is bound by the per-wave LDS instruction rate
 // (tools/probe_lds_bcast.cpp).  Here the four waves of the FIRST half produce them once per tile in their vector segment (three fragments each:
 // six transposing reads + three ds_write_b128 into a "fragment-major" slot, fragment f of lane l at f KiB + 16 l), and every wave reads them
 // back in its matrix segment with 12 ds_read_b128: 64 -> 52 LDS instructions per tile and wave where it counts.  Two slots of 12 KiB (tile t - 1 is
 // still read by the second half while the first half writes tile t).
-#ifndef ORV_BW_NO_FRAGBUF
-#define ORV_BW_FRAGBUF 1
-#endif
-#ifdef ORV_BW_FRAGBUF
 constexpr int DKV_FRAG0 = 7 * TILE + 7 * 256, DKV_FRAG_SLOT = 12 * 1024, DKV_SMEM = DKV_FRAG0 + 2 * DKV_FRAG_SLOT;
-#else
-constexpr int DKV_SMEM = 0;
-#endif
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p) {
-#ifdef ORV_BW_FRAGBUF
     extern __shared__ __attribute__((aligned(16))) char smem[];              // Q' slots 0-3 | dO slots 0-2 | lse x4 | delta x3 | fragment slots x2
-#else
-    __shared__ __attribute__((aligned(16))) char smem[7 * TILE + 7 * 256];   // Q' slots 0-3 | dO slots 0-2 | lse x4 | delta x3
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wq = wave & 3;
@@ -724,9 +671,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
     char* const vdst = smem + 7 * TILE + grp * 4 * 256;
     auto stage = [&](int t) {
         if (t >= nt) return;
-#ifdef ORV_BW_ABL_NODMA
-        if (t > 1) return;
-#endif
         const int slot_ = grp == 0 ? (t & 3) : t % 3;       // Q': four slots (staged two tiles ahead from the vector segment), dO: three
         char* const d = sdst + slot_ * TILE;
         if (__builtin_expect(ragged && t == nt - 1, 0)) {
@@ -773,9 +717,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
         const float* sL = (const float*)(smem + 7 * TILE + (t & 3) * 256);
         const float* sDl = (const float*)(smem + 7 * TILE + 4 * 256 + (t % 3) * 256);
         auto rd = [&](const char* base, int qb, int ks) {
-#ifdef ORV_BW_ABL_NOB128
-            bf16x8 z; asm volatile("" : "=v"(z)); return z;
-#endif
             return *(const bf16x8*)(base + qb * 4096 + (((ks * 2 + hi) ^ sw) * 16)); };
         auto init = [&](const float* v, int qb) {   // accumulator init: v[q(r)], q(r) = qb * 32 + (r & 3) + 8 (r >> 2) + 4 hi
             f32x16 c;
@@ -788,16 +729,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
         };
         bf16x8 qa0, oa0, qa1, oa1, qb0, ob0, qb1, ob1, o2, o3, g2_, g3_;
         if (t > 0) {
-            const char* sQp = smem + ((t - 1) & 3) * TILE;               // Q' and dO of the previous tile, transposed reads
+            // sQp / sOp (here and below) are unused since the fragment buffer replaced the transposing reads of k-steps 1-3.  They stay:
+            // without them hipcc allocates this kernel's registers differently, and a clean-up must not change the device code.
+            const char* sQp = smem + ((t - 1) & 3) * TILE;
             const char* sOp = smem + 4 * TILE + ((t - 1) % 3) * TILE;
-#ifdef ORV_BW_FRAGBUF
             const char* fb = smem + DKV_FRAG0 + ((t - 1) & 1) * DKV_FRAG_SLOT + lane * 16;
             o2 = *(const bf16x8*)(fb + 0 * 1024); o3 = *(const bf16x8*)(fb + 3 * 1024);
             g2_ = *(const bf16x8*)(fb + 6 * 1024); g3_ = *(const bf16x8*)(fb + 9 * 1024);
-#else
-            o2 = tr_pair(sOp + 2048 + t00, sOp + 2048 + t01); o3 = tr_pair(sOp + 2048 + t10, sOp + 2048 + t11);
-            g2_ = tr_pair(sQp + 2048 + t00, sQp + 2048 + t01); g3_ = tr_pair(sQp + 2048 + t10, sQp + 2048 + t11);
-#endif
         }
         BW_FENCE()
         stage_q();
@@ -809,25 +747,15 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
             dv[0] = BW_MFMA(o0, pf[0].v, dv[0]); dv[1] = BW_MFMA(o1, pf[0].v, dv[1]);
             dk[0] = BW_MFMA(g0_, dsf[0].v, dk[0]); dk[1] = BW_MFMA(g1_, dsf[0].v, dk[1]);
             BW_FENCE()
-#ifdef ORV_BW_FRAGBUF
             const char* fb = smem + DKV_FRAG0 + ((t - 1) & 1) * DKV_FRAG_SLOT + lane * 16;
             o0 = *(const bf16x8*)(fb + 1 * 1024); o1 = *(const bf16x8*)(fb + 4 * 1024);
             g0_ = *(const bf16x8*)(fb + 7 * 1024); g1_ = *(const bf16x8*)(fb + 10 * 1024);
-#else
-            o0 = tr_pair(sOp + 4096 + t00, sOp + 4096 + t01); o1 = tr_pair(sOp + 4096 + t10, sOp + 4096 + t11);
-            g0_ = tr_pair(sQp + 4096 + t00, sQp + 4096 + t01); g1_ = tr_pair(sQp + 4096 + t10, sQp + 4096 + t11);
-#endif
             BW_FENCE()
             dv[0] = BW_MFMA(o2, pf[1].v, dv[0]); dv[1] = BW_MFMA(o3, pf[1].v, dv[1]);
             dk[0] = BW_MFMA(g2_, dsf[1].v, dk[0]); dk[1] = BW_MFMA(g3_, dsf[1].v, dk[1]);
             BW_FENCE()
-#ifdef ORV_BW_FRAGBUF
             o2 = *(const bf16x8*)(fb + 2 * 1024); o3 = *(const bf16x8*)(fb + 5 * 1024);
             g2_ = *(const bf16x8*)(fb + 8 * 1024); g3_ = *(const bf16x8*)(fb + 11 * 1024);
-#else
-            o2 = tr_pair(sOp + 6144 + t00, sOp + 6144 + t01); o3 = tr_pair(sOp + 6144 + t10, sOp + 6144 + t11);
-            g2_ = tr_pair(sQp + 6144 + t00, sQp + 6144 + t01); g3_ = tr_pair(sQp + 6144 + t10, sQp + 6144 + t11);
-#endif
             BW_FENCE()
             dv[0] = BW_MFMA(o0, pf[2].v, dv[0]); dv[1] = BW_MFMA(o1, pf[2].v, dv[1]);
             dk[0] = BW_MFMA(g0_, dsf[2].v, dk[0]); dk[1] = BW_MFMA(g1_, dsf[2].v, dk[1]);
@@ -866,7 +794,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
     };
     // fragment (operand op = wq >> 1: 0 = dO^T, 1 = Q'^T; d block db = wq & 1; k-step ks) of tile t -> slot t & 1, index (op * 2 + db) * 3 + ks - 1
     auto produce_frags = [&](int t) {
-#ifdef ORV_BW_FRAGBUF
         const int op = wq >> 1, db = wq & 1;
         const char* base = op == 0 ? smem + 4 * TILE + (t % 3) * TILE : smem + (t & 3) * TILE;
         const int ta = db ? t10 : t00, tb = db ? t11 : t01;
@@ -874,18 +801,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
         const bf16x8 f1 = tr_pair(base + 2048 + ta, base + 2048 + tb), f2 = tr_pair(base + 4096 + ta, base + 4096 + tb),
                      f3 = tr_pair(base + 6144 + ta, base + 6144 + tb);
         *(bf16x8*)(fdst) = f1; *(bf16x8*)(fdst + 1024) = f2; *(bf16x8*)(fdst + 2048) = f3;
-#endif
     };
     auto seg_y = [&](int t) {
         prefetch_g(t);
         BW_FENCE()
-#ifdef ORV_BW_FRAGBUF
         if (grp == 0) { produce_frags(t); BW_FENCE() }
-#endif
-#ifdef ORV_BW_ABL_NOY
-        asm volatile("" ::"v"(sS[0]), "v"(sS[1]), "v"(dP[0]), "v"(dP[1]));
-        return;
-#endif
         // (rows of keys >= S compute garbage that is never stored; only query rows >= S must not contribute: ragged last tile only,
         // as a uniform branch ahead of the element loop - see attn_bwd_dq_pp_kernel)
         if (__builtin_expect(ragged && t == nt - 1, 0)) {
@@ -920,22 +840,16 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     BW_BAR()
     const bool act = __builtin_amdgcn_readfirstlane((int)(k0 < p.S)) != 0;
-    SEG_DECL
     if (grp == 0) {
         if (act) {
             for (int t = 0; t < nt; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() {});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // Q'_{t+1} landed (issued in Y_{t-1} / the prologue)
-                SEG_T(1)
                 BW_BAR()
-                SEG_T(2)
                 stage(t + 2);                                    // Q'_{t+2} -> slot of Q'_{t-2} (last read in the partners' X_{t-1}, two intervals ago)
                 BW_FENCE()
                 seg_y(t);
-                SEG_T(3)
                 BW_BAR()
-                SEG_T(4)
             }
             seg_x(nt, [&]() {});
         } else {
@@ -952,18 +866,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
         BW_BAR()
         if (act) {
             for (int t = 0; t < nt; ++t) {
-                SEG_T(0)
                 seg_x(t, [&]() {});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                SEG_T(1)
                 BW_BAR()
-                SEG_T(2)
                 stage(t + 2);                                    // dO_{t+2} -> slot of dO_{t-1} (last read in this half's X_t)
                 BW_FENCE()
                 seg_y(t);
-                SEG_T(3)
                 BW_BAR()
-                SEG_T(4)
             }
             seg_x(nt, [&]() {});
         } else {
@@ -975,7 +884,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_pp_kernel(const BwdArgs p
             }
         }
     }
-    SEG_DUMP(1)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int key = k0 + l31;
     if (key < p.S) {
@@ -1109,13 +1017,6 @@ extern "C" int orv_head_transpose(const void* src, int ld, int col0, void* dst, 
 // qT / kT / doT (per-head transposed copies written by orv_head_transpose) feed the two-pass kernels of rounds 1-2 only; with all
 // three NULL - what the host passes since round 3 - the ping-pong kernels read K^T / Q'^T / dO^T with transposing LDS reads from the
 // row-major tiles.  ORV_ATTN_BWD_PP=0 + non-NULL copies: the old kernels (A/B).
-#ifdef ORV_SEG_TRACE
-extern "C" int orv_debug_attn_bwd_trace(void* buf) {      // variant builds only: where the kernels leave their segment times
-    unsigned long long* q = (unsigned long long*)buf;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_bwd_trace), &q, sizeof(q)) == hipSuccess ? 0 : 1;
-}
-#endif
-
 namespace {
 // per-device side stream + fork / join events of orv_attention_bwd (created on first use, kept)
 struct BwdSide { hipStream_t stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool ok = false, tried = false; };
@@ -1156,7 +1057,7 @@ extern "C" int orv_attention_bwd(const void* qkv, int ld_qkv, const void* qT, co
     a.dout = (const bf16_t*)dout; a.ld_do = ld_out; a.neg_lse2 = neg_lse2; a.neg_delta = neg_delta;
     a.dqkv = (bf16_t*)dqkv; a.ld_dqkv = ld_dqkv; a.B = B; a.S = S; a.H = H; a.s_pad = s_pad; a.scale = scale;
     dim3 grid(((S + 255) / 256) * H * B);   // 1-D: orv_xcd_item hands head-major items to the XCDs
-    if (pp && DKV_SMEM > 0) {
+    if (pp) {
         static bool attr_done = false;
         if (!attr_done) { (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_SMEM); attr_done = true; }
     }

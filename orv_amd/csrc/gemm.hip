@@ -451,7 +451,7 @@ __global__ __launch_bounds__(512) void conv_strip_kernel(const GemmArgs p, const
 //     g-1), so after the barrier both waves of a SIMD have MFMAs ready at once: the matrix pipe never waits for LDS.
 //     The ds_reads of sub-stage g+1 and the wave's DMA pieces of sub-stage g+NSLOT-1 are issued between the 12
 //     v_mfma_f32_32x32x16_bf16 of sub-stage g.
-//   * Measured alternatives on this chip (tools/abl.sh, tools/trace_gemm.cpp): a 2-stage BK=64 double buffer with one
+//   * Measured alternatives on this chip (profiles/HISTORY.md): a 2-stage BK=64 double buffer with one
 //     vmcnt(0)+barrier per tile, and a strict ping-pong of two 4-wave groups (one computing, one reading LDS, a barrier
 //     per phase) both stall the matrix pipe ~45 % of the time - the first on lock-step LDS latency + DMA issue bursts,
 //     the second on the barrier itself (only one wave per SIMD ever has MFMAs to issue).
@@ -535,16 +535,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, char* smem, co
     static_assert(AHEAD * NPC + NSTORE <= 63, "vmcnt immediate is 6 bits");
     int st_pending = 0;                   // sub-stages whose DMA pieces were issued before the last epilogue's stores
 
-#ifdef ORV_GEMM_ABLATE_NOMFMA
-#define ORV_MFMA(FA, FB, kk, i, j) asm volatile("" ::"v"(FB[kk][i]), "v"(FA[kk][j]));
-#else
 #define ORV_MFMA(FA, FB, kk, i, j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FB[kk][i], FA[kk][j], acc[i][j], 0, 0, 0);
-#endif
-#ifdef ORV_GEMM_ABLATE_NOLOAD
-#define ORV_ISSUE_MAIN()
-#else
-#define ORV_ISSUE_MAIN() ORV_ISSUE_PIECES()
-#endif
     // one sub-stage: counted DMA wait + barrier (sub-stage g+1 is complete in LDS, slot g-1 is free), then
     //   ds_reads of g+1 -> fragment set NXT | MFMAs of g on fragment set CUR | DMA pieces of g+NSLOT-1 -> slot g-1
 #define ORV_SUBSTAGE(FA_CUR, FB_CUR, FA_NXT, FB_NXT)                                                                 \
@@ -558,7 +549,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, char* smem, co
         __builtin_amdgcn_s_barrier();                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
         ORV_READ_FRAGS(FA_NXT, FB_NXT)                                                                               \
-        ORV_ISSUE_MAIN()                                                                                             \
+        ORV_ISSUE_PIECES()                                                                                           \
         _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                             \
             _Pragma("unroll") for (int i = 0; i < NB; ++i)                                                           \
                 _Pragma("unroll") for (int j = 0; j < MB; ++j) { ORV_MFMA(FA_CUR, FB_CUR, kk, i, j) }                \
@@ -596,7 +587,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, char* smem, co
         const char* sb1_ = smem + rd_slot * SLOT;                                                                    \
         rd_slot = (rd_slot + 1 == NSLOT) ? 0 : rd_slot + 1;                                                          \
         ORV_READ_K(0)                                                                                                \
-        ORV_ISSUE_MAIN()                                                                                             \
+        ORV_ISSUE_PIECES()                                                                                           \
         _Pragma("unroll") for (int i = 0; i < NB; ++i)                                                               \
             _Pragma("unroll") for (int j = 0; j < MB; ++j) { ORV_MFMA(fa0, fb0, 0, i, j) }                           \
         __builtin_amdgcn_sched_group_barrier(0x100, MB + NB, 0);                                                     \
@@ -625,14 +616,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, char* smem, co
         __builtin_amdgcn_s_barrier();
     }
     ORV_READ_FRAGS(fa0, fb0)
-#ifdef ORV_GEMM_TRACE   // tools/trace_gemm.cpp: s_memtime stamps of workgroup 0 / wave 0 (R doubles as the trace buffer, EPI 0/1 only)
-    int trace_i = 0;
-#define ORV_TRACE(SLOT) if (blockIdx.x == 0 && threadIdx.x == 0 && trace_i < 16) ((unsigned long long*)p.R)[trace_i * 4 + SLOT] = __builtin_readcyclecounter();
-#else
-#define ORV_TRACE(SLOT)
-#endif
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        ORV_TRACE(0)
         for (int j = 0; j < nsub; j += 2) {            // K % 64 == 0, so nsub is even: static fragment-set names
             if constexpr (ONESET) {
                 ORV_SUBSTAGE1()
@@ -648,10 +632,8 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, char* smem, co
         // next tile's MFMAs instead of stalling the wave here.  Exact store count is needed for that, so tiles with rows
         // past M (predicated stores) and launches with a Y output keep the plain drain.
         int tm, tn;
-        ORV_TRACE(1)
         tile_of_index(p, tile, ntiles, tm, tn);
         gemm_epilogue<NB, MB, EPI>(p, acc, tm * BM + wq * 64, tn * BN + grp * (BN / 2), lane);
-        ORV_TRACE(2)
 #pragma unroll
         for (int i = 0; i < NB; ++i)
 #pragma unroll
@@ -663,10 +645,6 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, char* smem, co
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        ORV_TRACE(3)
-#ifdef ORV_GEMM_TRACE
-        ++trace_i;
-#endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef ORV_SETUP_SRC
@@ -674,11 +652,9 @@ __device__ __forceinline__ void gemm_ring_body(const GemmArgs& p, char* smem, co
 #undef ORV_ISSUE_PIECES
 #undef ORV_READ_FRAGS
 #undef ORV_MFMA
-#undef ORV_ISSUE_MAIN
 #undef ORV_SUBSTAGE
 #undef ORV_SUBSTAGE1
 #undef ORV_READ_K
-#undef ORV_TRACE
 }
 
 template <int BN, int NSLOT, int EPI>
@@ -736,16 +712,8 @@ __global__ __launch_bounds__(512) void gemm_ph_kernel(const GemmArgs p) {
     const bf16_t *sA0[APH], *sA1[APH], *sB0[BPH], *sB1[BPH];
     int kA0 = 0, kA1 = 0, kB0 = 0, kB1 = 0;
     int tA0 = blockIdx.x, tA1 = blockIdx.x, tB0 = blockIdx.x, tB1 = blockIdx.x;
-#ifdef ORV_PH_ABLATE_NODMA      /* ablation builds (tools/ph_abl.sh): separate compilations, never a run-time branch */
-#define ORV_PH_GLDS(G, L) asm volatile("" ::"v"(G));
-#else
 #define ORV_PH_GLDS(G, L) glds16(G, L);
-#endif
-#ifdef ORV_PH_ABLATE_NOMFMA
-#define ORV_PH_ONE_MFMA(B_, A_, C_) asm volatile("" ::"v"(B_), "v"(A_));
-#else
 #define ORV_PH_ONE_MFMA(B_, A_, C_) C_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(B_, A_, C_, 0, 0, 0);
-#endif
 #define ORV_PH_SETUP_A(H, ARR, TILE)                                                                                 \
     {                                                                                                                \
         int tm_, tn_;                                                                                                \
@@ -1094,8 +1062,6 @@ static const GemmCand* choose_tile(int M, int N, int K, int epilogue = 0, int he
         // the same kernel on 192-row tiles (gemm_t8r192_kernel, round 5): M = 3226 (one clip) is 17 row tiles, M = 6452 is 34 - 510 / 255 / 170 tiles
         // for N = 7680 / 3840 / 1920 where 256 rows give 390 / 195 / 130; at M = 12904 the 256-row tiles stay cheaper (rates: T8R192_RATE_*)
         {3, 192, 256, T8R192_RATE_256, 0}, {3, 192, 192, T8R192_RATE_192, 0},
-        // ring = 4: four-wave 256 x 256 experiment of gemm_t8.hip - forced only (rate 0.01 never wins)
-        {4, 256, 256, 0.01f, 0},
         // ring = 5: gemm_d8.hip (round 5) - A straight to registers two K-tiles ahead, W through four LDS buffers; needs K % 192 == 0
         {5, 256, 256, D8_RATE_256, 0}, {5, 256, 192, D8_RATE_192, 0}, {5, 256, 128, D8_RATE_128, 0},
         // the d8 kernel on 192-row tiles (gemm_d8r192_kernel, round 6): the first wave of every SIMD owns two 16-row blocks, the second one.
@@ -1134,7 +1100,6 @@ static const GemmCand* choose_tile(int M, int N, int K, int epilogue = 0, int he
         if (c.ring == 3 && c.bm == 192 && (off.r192 || epilogue == 3)) continue;
         // packed C has orv_packed_rows(M) = ceil(M / 256) * 256 row slots and the packed store is not masked: the 192-row tiling must fit them
         if (c.ring == 3 && c.bm == 192 && cpacked && (long)((M + 191) / 192) * 192 > (long)((M + 255) / 256) * 256) continue;
-        if (c.ring == 4 && (K % 128 != 0 || wide || epilogue > 2 || force_ring != 4)) continue;
         // ring 5 reads A in the packed P16 layout and nothing else does: the caller's a_packed decides the family
         if ((c.ring == 5) != packed) continue;
         // packed C from row-major A: only the t8 kernel's 256-wide GELU epilogue writes it
@@ -1222,7 +1187,6 @@ static int gemm_dispatch(GemmArgs a, const GemmCand* best, int epilogue, hipStre
     static const int gm_env = orv_env_int("ORV_GEMM_GM", 0);
     a.gm = gm_env > 0 ? gm_env : (a.K >= 4096 && a.tiles_n <= 16 ? 8 : 0);
     if (best->ring == 3) return launch_t8(a, best->bn, epilogue, st, best->bm);
-    if (best->ring == 4) return launch_t4(a, epilogue, st);
     if (best->ring == 5) return launch_d8(a, best->bn, epilogue, st, best->bm);
     if (best->ring == 2) {
         if (best->bn == 256) return launch_ph<256>(a, epilogue, st);

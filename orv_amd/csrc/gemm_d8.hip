@@ -60,40 +60,14 @@ __device__ __forceinline__ unsigned long long d8_uniform64(unsigned long long u)
 // Row-operand epilogues (2 = gated residual, 3 = GELU adjoint).  Up to round 6 the rows of a 64-column group were requested when the group
 // started, the bias behind them and the gate values inside the row-block loop, each used at once: every one of those loads sat BEHIND the
 // previous stores, and since the vector-memory counter retires in order, waiting for it meant waiting for those stores' acknowledgements too -
-// 41 full drains in gemm_d8_kernel<192, 2> against 10 in the plain kernel.  A second residual register set (D8_RSETS = 2, round 5) and the
-// slab below only moved the residual rows and left that chain in place, which is why both measured level.  Now d8_epilogue gathers bias and
+// 41 full drains in gemm_d8_kernel<192, 2> against 10 in the plain kernel.  A second residual register set (round 5) and residual rows
+// staged by LDS-DMA only moved the residual rows and left that chain in place, which is why both measured level.  Now d8_epilogue gathers bias and
 // gate before the tile's first store and rolls ONE residual set a group ahead (profiles/r7_gemm_gated_epilogue.txt).
-// RLDS (opt-in experiment, BN <= 192 where 32 KiB of LDS are free): the residual rows of a 64-column group arrive by LDS-DMA in a per-wave
-// 4-KiB slab ([32 rows][128 B], full-line pieces) - group 0's is issued three K-tiles before the K loop ends (d8_issue_rows from the kernel),
-// group g + 1's as soon as group g's rows have been read out of the slab.  It still drains once per group.
-__device__ __forceinline__ void d8_glds_v(const void* gsrc, const char* lds_dst) {
-    const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)lds_dst);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(gsrc), "s"(d) : "memory", "m0");
-}
-__device__ __forceinline__ void d8_issue_rows(const GemmArgs& p, const int row0, const int colg, const int lane, const char* slab) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int mc = min(row0 + 8 * j + (lane >> 3), p.M - 1);
-        long rr = mc;
-        if (p.r_mod > 0) rr = mc % p.r_mod;
-        else if (p.c_rows > 0) rr = (long)(mc / p.c_rows) * p.c_bstride + p.c_off + mc % p.c_rows;
-        d8_glds_v(p.R + rr * p.ldr + colg + 8 * (lane & 7), slab + j * 1024);
-    }
-}
-template <int BN, int EPI>
-constexpr bool d8_rlds() {
-#ifdef ORV_D8_RLDS       // opt-in build: measured level with the register loads (profiles/r5_gemm_d8_rlds.txt: FFN2 0.2907 vs 0.2903 ms, out-projection
-    return BN <= 192 && (EPI == 2 || EPI == 3);     // 0.0953 vs 0.0945) - it moved the residual rows only, the bias and gate loads kept the chain
-#else
-    return false;
-#endif
-}
 
 template <int BN, int EPI, int RB = 2>
 __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][BN / 16], const int row0, const int col0, const int lane,
-                                            char* const scr, const char* const rslab = nullptr) {
+                                            char* const scr) {
     constexpr int NG = BN / 64;
-    constexpr bool RLDS = d8_rlds<BN, EPI>();
     const int g = lane >> 4, r16 = lane & 15;
     const int c = lane & 7, rr8 = lane >> 3;
     int woff[4];
@@ -168,23 +142,7 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
         if (p.r_mod > 0) rr = min(row0 + rb * 16 + 8 * j + rr8, p.M - 1) % p.r_mod;
         return *(const uint4*)(p.R + rr * p.ldr + col0 + 64 * cg + 8 * c);
     };
-    // RLDS: rows of group cg out of the slab (the DMA was issued by the kernel / by the previous group), then the next group's DMA
-    auto take_rows = [&](int cg, uint4 (&dst)[RB][2]) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) dst[rb][j] = *(const uint4*)(rslab + (rb * 16 + 8 * j + rr8) * 128 + c * 16);
-        if (cg + 1 < NG) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            d8_issue_rows(p, row0, col0 + 64 * (cg + 1), lane, rslab);
-        }
-    };
-    if (RLDS) {
-        take_rows(0, r8);
-    } else if (GATH) {
+    if (GATH) {
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -226,7 +184,6 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
 #pragma unroll
     for (int cg = 0; cg < NG; ++cg) {
         const int col8 = col0 + 64 * cg + 8 * c;
-        if (RLDS && cg > 0) take_rows(cg, r8);
         float b8[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) b8[e] = 0.f;
@@ -285,7 +242,7 @@ __device__ __forceinline__ void d8_epilogue(const GemmArgs& p, f32x4 (&acc)[RB][
                 uint4 rcur;
                 if constexpr (GATH) {
                     rcur = r8[rb][j];
-                    if (!RLDS && cg + 1 < NG) r8[rb][j] = load_row(cg + 1, rb, j);
+                    if (cg + 1 < NG) r8[rb][j] = load_row(cg + 1, rb, j);
                 }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) w[e] += b8[e];
@@ -404,7 +361,6 @@ __device__ __forceinline__ void d8_epilogue_packed(const GemmArgs& p, f32x4 (&ac
 template <int BN, int EPI, int RB, int BM>
 __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
     static_assert(BM == 256 || BM == 192, "tile rows");
-    static_assert(!(d8_rlds<BN, EPI>() && BM != 256), "the residual slab path is written for 32-row waves");
     constexpr int NA = 2 * RB;                        // A loads per wave and K-tile
     constexpr int NCB = BN / 16;                      // 16-column blocks of the tile (16 / 12)
 #ifndef ORV_D8_CBP256
@@ -454,11 +410,7 @@ __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
         tW += w_ ? (int)gridDim.x : 0;                                                                               \
         _Pragma("unroll") for (int j = 0; j < ND; ++j) wb[j] = w_ ? wbn[j] : wb[j];                                  \
     }
-#ifdef ORV_D8_ABL_NODMA      // ablation builds (tools/d8_abl.sh, wrong results)
-#define D8_DMA1(OFF, SB, LDS) asm volatile("" :: "v"(OFF), "s"(SB), "s"(LDS));
-#else
 #define D8_DMA1(OFF, SB, LDS) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(OFF), "s"(SB), "s"(LDS) : "memory", "m0");
-#endif
 #define D8_ISSUE_W(BUFI)                                                                                             \
     {                                                                                                                \
         _Pragma("unroll") for (int j = 0; j < ND; ++j) {                                                             \
@@ -492,11 +444,7 @@ __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
         tA += w_ ? (int)gridDim.x : 0;                                                                               \
         ab = w_ ? abn : ab;                                                                                          \
     }
-#ifdef ORV_D8_ABL_NOA
-#define D8_LOADA(DST, OFF, SB, IMM) asm volatile("" : "=v"(DST) : "v"(OFF), "s"(SB));
-#else
 #define D8_LOADA(DST, OFF, SB, IMM) asm volatile("global_load_dwordx4 %0, %1, %2 offset:" #IMM : "=v"(DST) : "v"(OFF), "s"(SB) : "memory");
-#endif
 #define D8_ISSUE_A(SET)                                                                                              \
     {                                                                                                                \
         const unsigned long long sa_ = ab + (unsigned long long)kA * 2048;                                           \
@@ -524,23 +472,10 @@ __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
     // W fragment F[t][kh] of a phase = column block PH * CBP + t, k half kh.  ONE fragment set, rolling: step s = kh * CBP + t of a phase
     // issues the two MFMAs (row blocks 0, 1) of F[t][kh] and then re-requests the SAME registers for the next phase - the read has a whole
     // phase (4 CBP MFMAs) to land, reads and MFMAs alternate 1 : 2 instead of arriving in bursts, and no second fragment set is needed.
-#ifdef ORV_D8_ABL_NOREAD
-#define D8_READ1(T, KH, BOFF, PH) asm volatile("" : "+v"(fx[T][KH]));
-#elif defined(ORV_D8_ABL_READ2)   // experiment (right results): every fragment is read TWICE (the second copy is thrown away) - what do LDS reads cost in time / energy?
-#define D8_READ1(T, KH, BOFF, PH)                                                                                    \
-    { fx[T][KH] = *(const bf16x8*)(((KH) ? rd1 : rd0) + (BOFF) + ((PH) * CBP + (T)) * 2048);                         \
-      bf16x8 dummy_ = *(const volatile bf16x8*)(((KH) ? rd0 : rd1) + (BOFF) + ((PH) * CBP + (T)) * 2048); asm volatile("" :: "v"(dummy_)); }
-#else
 #define D8_READ1(T, KH, BOFF, PH) fx[T][KH] = *(const bf16x8*)(((KH) ? rd1 : rd0) + (BOFF) + ((PH) * CBP + (T)) * 2048);
-#endif
-#ifdef ORV_D8_ABL_NOMFMA
-#define D8_MFMA1(T, KH, AS, PH)                                                                                      \
-    _Pragma("unroll") for (int rb = 0; rb < RB; ++rb) asm volatile("" : "+v"(acc[rb][(PH) * CBP + (T)]) : "v"(fx[T][KH]), "v"(AS[rb * 2 + (KH)]));
-#else
 #define D8_MFMA1(T, KH, AS, PH)                                                                                      \
     _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                                                \
         acc[rb][(PH) * CBP + (T)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[T][KH], AS[rb * 2 + (KH)], acc[rb][(PH) * CBP + (T)], 0, 0, 0);
-#endif
     // One vector-memory instruction of this K-tile's group: slots 0 .. ND - 1 = the W pieces of K-tile u + 3 (into buffer DBUF), slots ND ..
     // ND + 3 = the A loads of K-tile u + 2 (into ANEW).  The slots are SPREAD over the phases, each between the two k halves of a phase's MFMAs:
     // issued together behind the barrier (the first build) the eight waves' 64 instructions queue at the texture path for ~1000 cycles during
@@ -573,46 +508,17 @@ __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
         D8_READ1(s_ % CBP, s_ / CBP, RBUF, RPH) D8_FENCE()                                                           \
         D8_STEP_SLOT(PH, s_, ANEW, DBUF) D8_FENCE()                                                                  \
     }
-#ifdef ORV_D8_ABL_NOWAIT     // ablation (wrong results): is the K loop waiting for its own loads?
-#define D8_WAIT(ACUR)                                                                                                \
-    if constexpr (RB == 2) asm volatile("" : "+v"(ACUR[0]), "+v"(ACUR[1]), "+v"(ACUR[2]), "+v"(ACUR[3]));            \
-    else asm volatile("" : "+v"(ACUR[0]), "+v"(ACUR[1]));
-#else
 #define D8_WAIT(ACUR)                                                                                                \
     if constexpr (RB == 2) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(ACUR[0]), "+v"(ACUR[1]), "+v"(ACUR[2]), "+v"(ACUR[3]) : "n"(ND + NA) : "memory"); \
     else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(ACUR[0]), "+v"(ACUR[1]) : "n"(ND + NA) : "memory");
-#endif
     // One K-tile u.  ACUR: the A set it computes with; ANEW: the set K-tile u - 1 used, refilled for K-tile u + 2.  bufc = u & 3.
     //   wait: this wave's group of two K-tiles ago = { W pieces of K-tile u + 1, A of K-tile u } (the group of K-tile u - 1 stays in flight)
     //   barrier: every wave's pieces of K-tile u + 1 have landed, every wave is done with the buffer of K-tile u - 1
     //   NPH phases; the last one re-requests K-tile u + 1's first fragments (complete since the barrier above);
     //   this K-tile's group (W pieces of K-tile u + 3 into the buffer of K-tile u - 1, A of K-tile u + 2) is issued slot by slot
-    // -DORV_D8_ABL_LNA (ablation, right results): what would it cost to apply the LayerNorm-modulate to the A operand on its way into the MFMA
-    // (drop the 1.39 ms LayerNorm pass, the producing epilogues emit row statistics)?  Every A element of the K-tile just waited
-    // for goes through the arithmetic that fusion needs - unpack, (x - mean) rstd as one FMA with per-row constants, * (1 + scale) + shift as
-    // one FMA with per-column constants, round to bf16 - with IDENTITY constants taken from the argument block (the compiler cannot fold them).
-    // The per-column factor loads (a second small LDS / L2 stream per K-tile and token group) are NOT included: a lower bound of the cost.
-#ifdef ORV_D8_ABL_LNA
-    const float lna_rs = p.qn_eps == 12345.f ? 2.f : 1.f, lna_nm = p.qn_eps == 12345.f ? 1.f : 0.f;      // per-row: rstd, -mean rstd
-    float lna_g[8], lna_s[8];                                                                             // per-column: 1 + scale, shift
-    _Pragma("unroll") for (int e_ = 0; e_ < 8; ++e_) { lna_g[e_] = p.qn_premul == 54321.f ? 3.f + e_ : 1.f; lna_s[e_] = p.qn_premul == 54321.f ? 1.f : 0.f; }
-#define D8_LNA(ACUR)                                                                                                 \
-    _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_) {                                                              \
-        union { bf16x8 v; uint32_t u[4]; } c_; c_.v = ACUR[i_];                                                      \
-        _Pragma("unroll") for (int w_ = 0; w_ < 4; ++w_) {                                                           \
-            const float lo_ = __builtin_fmaf(__builtin_fmaf(bf2f(c_.u[w_] & 0xffff), lna_rs, lna_nm), lna_g[2 * w_], lna_s[2 * w_]);          \
-            const float hi_ = __builtin_fmaf(__builtin_fmaf(bf2f(c_.u[w_] >> 16), lna_rs, lna_nm), lna_g[2 * w_ + 1], lna_s[2 * w_ + 1]);     \
-            c_.u[w_] = pack2bf(lo_, hi_);                                                                            \
-        }                                                                                                            \
-        ACUR[i_] = c_.v;                                                                                             \
-    }
-#else
-#define D8_LNA(ACUR)
-#endif
 #define D8_KTILE(ACUR, ANEW)                                                                                         \
     {                                                                                                                \
         D8_WAIT(ACUR)                                                                                                \
-        D8_LNA(ACUR)                                                                                                 \
         D8_FENCE() __builtin_amdgcn_s_barrier(); D8_FENCE()                                                          \
         const int cur_ = bufc * BUFSZ, nxt_ = ((bufc + 1) & 3) * BUFSZ, dbuf_ = (bufc + 3) & 3;                      \
         _Pragma("unroll") for (int pp_ = 0; pp_ < NPH; ++pp_) {                                                      \
@@ -636,23 +542,14 @@ __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
         D8_SETUP_W(wbn, tW + (int)gridDim.x)
         D8_SETUP_A(abn, tA + (int)gridDim.x)
         for (int kt = 0; kt < nk; kt += 3) {
-            if (d8_rlds<BN, EPI>() && kt + 3 >= nk) {      // the epilogue's first residual rows: in flight under the last three K-tiles
-                int tm_, tn_;
-                tile_of_index(p, tile, ntiles, tm_, tn_);
-                d8_issue_rows(p, tm_ * BM + wrb * 16, tn_ * BN, lane, smem + SCR + 8 * 4096 + wave * 4096);
-            }
             D8_KTILE(a0, a2)
             D8_KTILE(a1, a0)
             D8_KTILE(a2, a1)
         }
         int tm, tn;
         tile_of_index(p, tile, ntiles, tm, tn);
-#ifdef ORV_D8_ABL_NOEPI      // ablation (wrong results): the kernel without its epilogue = what PERFECTLY hidden epilogues would leave
-        _Pragma("unroll") for (int a_ = 0; a_ < RB; ++a_)
-            _Pragma("unroll") for (int b_ = 0; b_ < NCB; ++b_) asm volatile("" :: "v"(acc[a_][b_]));      // every MFMA stays
-#else
         if ((EPI == 0 || EPI == 1) && p.c_packed) d8_epilogue_packed<BN, EPI, RB>(p, acc, tm * BM + wrb * 16, tn * BN, lane);
-        else d8_epilogue<BN, EPI, RB>(p, acc, tm * BM + wrb * 16, tn * BN, lane, smem + SCR + wave * 4096, smem + SCR + 8 * 4096 + wave * 4096);
+        else d8_epilogue<BN, EPI, RB>(p, acc, tm * BM + wrb * 16, tn * BN, lane, smem + SCR + wave * 4096);
         // BN = 256, row-operand epilogues: 128 accumulator registers + the A sets in flight + the next tile's first W fragments leave the
         // epilogue too few registers - it spilled, and every spill reload is a load behind a store (a full drain).  The fragments are read
         // AGAIN here instead of being kept across the epilogue (the buffer is complete since the last K-tile's barrier and is not refilled
@@ -662,7 +559,6 @@ __device__ __forceinline__ void d8_body(const GemmArgs& p, char* const smem) {
             _Pragma("unroll") for (int s_ = 0; s_ < 2 * CBP; ++s_) { D8_READ1(s_ % CBP, s_ / CBP, bufc * BUFSZ, 0) }
             D8_FENCE()
         }
-#endif
 #pragma unroll
         for (int a = 0; a < RB; ++a)
 #pragma unroll
@@ -688,7 +584,7 @@ __global__ __launch_bounds__(512) void gemm_d8r192_kernel(const GemmArgs p) {
 
 template <int BN, int EPI, int BM>
 int launch_d8_one(const GemmArgs& a, hipStream_t st) {
-    constexpr int smem = 4 * BN * 128 + 8 * 4096 + (d8_rlds<BN, EPI>() ? 8 * 4096 : 0);     // four W buffers + the epilogue scratch (160 KiB at BN = 256) + the residual slabs
+    constexpr int smem = 4 * BN * 128 + 8 * 4096;     // four W buffers + the epilogue scratch (160 KiB at BN = 256)
     void (*kern)(const GemmArgs);
     if constexpr (BM == 256) kern = gemm_d8_kernel<BN, EPI>;
     else kern = gemm_d8r192_kernel<BN, EPI>;

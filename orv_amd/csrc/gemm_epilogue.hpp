@@ -253,9 +253,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[N
                 }
                 swap_halves(oc[0][0], oc[1][0]);   // lower: (A cols 0-3 | A cols 4-7) ; upper: (B cols 0-3 | B cols 4-7)
                 swap_halves(oc[0][1], oc[1][1]);
-#ifdef ORV_GEMM_ABLATE_NOSTORE
-                if (p.dbg == 12345)
-#endif
                 *(uint4*)(crow + n16) = make_uint4(oc[0][0], oc[0][1], oc[1][0], oc[1][1]);
             }
         }

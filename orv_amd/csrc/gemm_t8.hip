@@ -23,11 +23,6 @@
 
 namespace {
 using namespace orv_gemm;
-#ifdef ORV_T8_SCHED3
-constexpr bool T8_SCHED3_ON = true;
-#else
-constexpr bool T8_SCHED3_ON = false;
-#endif
 
 __device__ __forceinline__ float sum_xor16(float v) {      // v(lane) + v(lane ^ 16)
     const unsigned u = __float_as_uint(v);
@@ -53,14 +48,10 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
 //             block 2:                              column 32 + 4 g + e              -> one 4-column piece
 template <int BN, int EPI, int MB = 4>      // MB: 16-row blocks per m half of a wave (4: 256-row tiles, 3: 192-row tiles)
 __device__ __forceinline__ void t8_epilogue(const GemmArgs& p, f32x4 (&acc)[2][MB][BN / 64], const int mbase, const int nbase, const int lane) {
+    static_assert(EPI == 1 || EPI == 4, "the register-layout epilogue serves GELU and qk LayerNorm; 0, 2, 3 go through t8_epilogue_lds");
     constexpr int NP = BN == 256 ? 2 : 1;            // 8-column pieces per row
     constexpr bool TAIL = BN == 192;                 // plus one 4-column piece
     const int g = lane >> 4, r16 = lane & 15;
-#ifdef ORV_T8_ABL_NOSTORE    // ablation build (tools/t8_epi_abl.sh, wrong results): the epilogue computes everything, no store is executed
-    const bool st_ok = p.M < 0;
-#else
-    constexpr bool st_ok = true;
-#endif
     int col8[NP];
 #pragma unroll
     for (int P = 0; P < NP; ++P) col8[P] = nbase + 32 * P + 8 * g;
@@ -113,7 +104,7 @@ __device__ __forceinline__ void t8_epilogue(const GemmArgs& p, f32x4 (&acc)[2][M
                 for (int P = 0; P < NP; ++P)
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { v[P][e] = acc[mh][mb][2 * P + (e >> 2)][e & 3] + b8[P][e]; s += v[P][e]; }
-                if (p.Y && valid && st_ok) {
+                if (p.Y && valid) {
 #pragma unroll
                     for (int P = 0; P < NP; ++P) *(uint4*)(p.Y + orow * p.ldy + col8[P]) = pack8(v[P]);
                 }
@@ -130,31 +121,18 @@ __device__ __forceinline__ void t8_epilogue(const GemmArgs& p, f32x4 (&acc)[2][M
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[P][e] = qkln_affine(v[P][e], rstd, ga[P][e], be[P][e], post);
                 }
-                if (valid && st_ok) {
+                if (valid) {
 #pragma unroll
                     for (int P = 0; P < NP; ++P) *(uint4*)(p.C + orow * p.ldc + col8[P]) = pack8(v[P]);
                 }
             }
         return;
     } else {
-        // gate row cache (EPI 2): 16-row blocks almost always lie inside one (batch element, token group) and consecutive blocks
-        // share it - the fp32 gate values of this lane's columns are reloaded only when the block's gate row changes
-        float g8[NP][8], g4[4];
-        const float* g_cached = nullptr;
-#pragma unroll
-        for (int P = 0; P < NP; ++P)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) g8[P][e] = 1.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g4[e] = 1.f;
-
+        // GELU (EPI 1)
 #pragma unroll
         for (int mh = 0; mh < 2; ++mh) {
-            // row operands of the four 16-row blocks of this half are requested together
-            long orow[MB], rr[MB];
+            long orow[MB];
             bool valid[MB];
-            uint4 r8[MB][NP];
-            uint2 r4[MB];
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 const int m = mbase + mh * (16 * MB) + mb * 16 + r16;
@@ -162,45 +140,9 @@ __device__ __forceinline__ void t8_epilogue(const GemmArgs& p, f32x4 (&acc)[2][M
                 const int mc = min(m, p.M - 1);
                 orow[mb] = mc;
                 if (p.c_rows > 0) orow[mb] = (long)(mc / p.c_rows) * p.c_bstride + p.c_off + mc % p.c_rows;
-                rr[mb] = p.r_mod > 0 ? mc % p.r_mod : orow[mb];
-                if (EPI == 2 || EPI == 3) {
-#pragma unroll
-                    for (int P = 0; P < NP; ++P) r8[mb][P] = *(const uint4*)(p.R + rr[mb] * p.ldr + col8[P]);
-                    if (TAIL) r4[mb] = *(const uint2*)(p.R + rr[mb] * p.ldr + col4);
-                }
             }
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
-                bool g_lane = false;             // block straddles a frame / text boundary: per-lane gate rows
-                const float* grow = nullptr;
-                if (EPI == 2 && p.gate) {
-                    const int mf = __builtin_amdgcn_readfirstlane(mbase + mh * (16 * MB) + mb * 16), ml = min(mf + 15, p.M - 1);
-                    long of = min(mf, p.M - 1), ol = ml;
-                    if (p.c_rows > 0) {
-                        of = (long)(of / p.c_rows) * p.c_bstride + p.c_off + of % p.c_rows;
-                        ol = (long)(ml / p.c_rows) * p.c_bstride + p.c_off + ml % p.c_rows;
-                    }
-                    const int bf_ = (int)(of / p.seq), bl_ = (int)(ol / p.seq);
-                    const int gf_ = orv_group_of((int)(of % p.seq), p.n_text, p.per_group);
-                    const int gl_ = orv_group_of((int)(ol % p.seq), p.n_text, p.per_group);
-                    if (bf_ == bl_ && gf_ == gl_) {
-                        const float* gr = p.gate + bf_ * p.gate_b + gf_ * p.gate_g;
-                        if (gr != g_cached) {
-                            g_cached = gr;
-#pragma unroll
-                            for (int P = 0; P < NP; ++P) {
-                                const float4 a = *(const float4*)(gr + col8[P]), b = *(const float4*)(gr + col8[P] + 4);
-                                g8[P][0] = a.x; g8[P][1] = a.y; g8[P][2] = a.z; g8[P][3] = a.w;
-                                g8[P][4] = b.x; g8[P][5] = b.y; g8[P][6] = b.z; g8[P][7] = b.w;
-                            }
-                            if (TAIL) { const float4 a = *(const float4*)(gr + col4); g4[0] = a.x; g4[1] = a.y; g4[2] = a.z; g4[3] = a.w; }
-                        }
-                    } else {
-                        g_lane = true;
-                        const int bidx = (int)(orow[mb] / p.seq), s = (int)(orow[mb] % p.seq);
-                        grow = p.gate + bidx * p.gate_b + orv_group_of(s, p.n_text, p.per_group) * p.gate_g;
-                    }
-                }
                 bf16_t* crow = p.C + orow[mb] * p.ldc;
                 bf16_t* yrow = p.Y ? p.Y + orow[mb] * p.ldy : nullptr;
 #pragma unroll
@@ -208,59 +150,25 @@ __device__ __forceinline__ void t8_epilogue(const GemmArgs& p, f32x4 (&acc)[2][M
                     float v[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = acc[mh][mb][2 * P + (e >> 2)][e & 3] + b8[P][e];
-                    if (yrow && valid[mb] && st_ok) *(uint4*)(yrow + col8[P]) = pack8(v);
-                    if (EPI == 1) {
+                    if (yrow && valid[mb]) *(uint4*)(yrow + col8[P]) = pack8(v);
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = gelu_tanh(v[e]);
-                    }
-                    if (EPI == 2) {
-                        float rv[8], gg[8];
-                        unpack8(r8[mb][P], rv);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) gg[e] = g8[P][e];
-                        if (g_lane) {
-                            const float4 a = *(const float4*)(grow + col8[P]), b = *(const float4*)(grow + col8[P] + 4);
-                            gg[0] = a.x; gg[1] = a.y; gg[2] = a.z; gg[3] = a.w; gg[4] = b.x; gg[5] = b.y; gg[6] = b.z; gg[7] = b.w;
-                        }
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = rv[e] + gg[e] * v[e];
-                    }
-                    if (EPI == 3) {
-                        float rv[8];
-                        unpack8(r8[mb][P], rv);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] *= gelu_tanh_grad(rv[e]);
-                    }
-                    if (BN == 256 && EPI == 1 && p.c_packed) {
+                    for (int e = 0; e < 8; ++e) v[e] = gelu_tanh(v[e]);
+                    if (BN == 256 && p.c_packed) {
                         // packed P16 output (orv_gemm_t.c_packed: the hidden state of FeedForward, cogvideox_control.py:439 -> :440, as the A
                         // operand of gemm_d8): lane (r16, g) holds columns 32 P + 8 g + (0..7) of row r16 = slot 16 g + r16 of packed block
                         // (row block, column block) - one lane-linear, contiguous 1-KiB store; the buffer has tiles_m * 256 row slots (no mask)
-                        if (st_ok) *(uint4*)((char*)p.C + ((((long)((mbase + mh * (16 * MB) + mb * 16) >> 4)) * (p.ldc >> 5) + ((nbase + 32 * P) >> 5)) << 10) + lane * 16) = pack8(v);
+                        *(uint4*)((char*)p.C + ((((long)((mbase + mh * (16 * MB) + mb * 16) >> 4)) * (p.ldc >> 5) + ((nbase + 32 * P) >> 5)) << 10) + lane * 16) = pack8(v);
                     } else
-                    if (valid[mb] && st_ok) *(uint4*)(crow + col8[P]) = pack8(v);
+                    if (valid[mb]) *(uint4*)(crow + col8[P]) = pack8(v);
                 }
                 if (TAIL) {
                     float v[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = acc[mh][mb][BN / 64 - 1][e] + b4[e];
-                    if (yrow && valid[mb] && st_ok) *(uint2*)(yrow + col4) = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
-                    if (EPI == 1) {
+                    if (yrow && valid[mb]) *(uint2*)(yrow + col4) = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
-                    }
-                    if (EPI == 2 || EPI == 3) {
-                        const float rv[4] = {bf2f(r4[mb].x & 0xffff), bf2f(r4[mb].x >> 16), bf2f(r4[mb].y & 0xffff), bf2f(r4[mb].y >> 16)};
-                        if (EPI == 2) {
-                            float gg[4] = {g4[0], g4[1], g4[2], g4[3]};
-                            if (g_lane) { const float4 a = *(const float4*)(grow + col4); gg[0] = a.x; gg[1] = a.y; gg[2] = a.z; gg[3] = a.w; }
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = rv[e] + gg[e] * v[e];
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] *= gelu_tanh_grad(rv[e]);
-                        }
-                    }
-                    if (valid[mb] && st_ok) *(uint2*)(crow + col4) = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
+                    for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
+                    if (valid[mb]) *(uint2*)(crow + col4) = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
                 }
             }
         }
@@ -269,7 +177,8 @@ __device__ __forceinline__ void t8_epilogue(const GemmArgs& p, f32x4 (&acc)[2][M
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Round 4: epilogue through a per-wave LDS transpose (the shipped one; -DORV_T8_EPI_DIRECT keeps the register-layout epilogue above).
+// Round 4: epilogue through a per-wave LDS transpose, for the plain, gated-residual and GELU-adjoint epilogues (0, 2, 3); GELU and qk
+// LayerNorm (1, 4) keep the register-layout epilogue above (gemm_t8_body.inc says why).
 // Why: in the accumulator layout lane (r = lane & 15, g = lane >> 4) owns 16-byte pieces of row r, so ONE store / residual-load
 // instruction touches 16 different rows and the four lanes that share a row's 64-byte segment are 16 lanes apart - the address
 // coalescer sees 64 separate 16-byte requests.  Measured (profiles/r4_gemm_epilogue_ablation.txt): the stores alone cost 10-12 % of
@@ -279,29 +188,16 @@ __device__ __forceinline__ void t8_epilogue(const GemmArgs& p, f32x4 (&acc)[2][M
 // 8-column chunk l & 7): 8 adjacent lanes hold one row's 128 contiguous bytes (BN = 256; 96 of them at BN = 192, lanes with chunk >= 6
 // idle), a store / load instruction is 8 rows x one full line.  Image: 16-byte chunk L of row r sits at chunk L ^ (r & 7)
 // (conflict-free for the 8-lane ds_write_b128 groups and the 16-lane ds_read_b128 groups).
-// The arithmetic is the register epilogue's, element for element (same fp32 expressions), so results are bit-identical to it.
-__device__ __forceinline__ float sum8(float v) {             // sum over the 8 lanes lane & ~7 .. lane | 7
-    v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
-    v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
-    v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0x141, 0xF, 0xF, true));    // row_half_mirror
-    return v;
-}
-
 template <int BN, int EPI, int MB = 4>
 __device__ __forceinline__ void t8_epilogue_lds(const GemmArgs& p, f32x4 (&acc)[2][MB][BN / 64], const int mbase, const int nbase, const int lane,
                                                 char* const scr) {
     constexpr int NBW = BN / 64;                     // 16-column accumulator blocks per wave
     constexpr int NC = BN / 32;                      // 8-column chunks per row of the wave (8 or 6)
-    static_assert(BN == 256 || EPI != 4, "epilogue 4 needs whole heads per wave");
+    static_assert(EPI == 0 || EPI == 2 || EPI == 3, "the LDS-transposed epilogue serves plain, gated residual and GELU adjoint; 1, 4 go through t8_epilogue");
     const int g = lane >> 4, r16 = lane & 15;        // accumulator side
     const int c = lane & 7, rr8 = lane >> 3;         // transposed side: row 8 j + rr8 of the block, columns 8 c .. 8 c + 7 of the wave
     const bool lane_on = c < NC;
     const int col8 = nbase + 8 * min(c, NC - 1);
-#ifdef ORV_T8_ABL_NOSTORE
-    const bool st_ok = p.M < 0;
-#else
-    constexpr bool st_ok = true;
-#endif
     // scratch offsets
     int woff[NBW];
 #pragma unroll
@@ -316,20 +212,6 @@ __device__ __forceinline__ void t8_epilogue_lds(const GemmArgs& p, f32x4 (&acc)[
     for (int e = 0; e < 8; ++e) b8[e] = 0.f;
     if (p.bias) unpack8(*(const uint4*)(p.bias + col8), b8);
 
-    // epilogue 4: qk LayerNorm parameters of this lane's 8 channels of the head
-    float ga[8], be[8];
-    int region = 2;
-    float post = 1.f;
-    if constexpr (EPI == 4) {
-        region = __builtin_amdgcn_readfirstlane(nbase / (p.qn_heads * 64));     // 0 = q, 1 = k, 2 = v
-        const bf16_t* gam = region == 0 ? p.qn_gq : p.qn_gk;
-        const bf16_t* bet = region == 0 ? p.qn_bq : p.qn_bk;
-        post = region == 0 ? p.qn_premul : 1.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { ga[e] = 1.f; be[e] = 0.f; }
-        if (region < 2 && gam) unpack8(*(const uint4*)(gam + 8 * c), ga);
-        if (region < 2 && bet) unpack8(*(const uint4*)(bet + 8 * c), be);
-    }
     // gate row cache (EPI 2): the fp32 gate values of this lane's 8 columns, reloaded only when the block's gate row changes
     float g8[8];
     const float* g_cached = nullptr;
@@ -407,25 +289,7 @@ __device__ __forceinline__ void t8_epilogue_lds(const GemmArgs& p, f32x4 (&acc)[
 #pragma unroll
                 for (int e = 0; e < 8; ++e) w[e] += b8[e];
                 bf16_t* crow = p.C + orow[mb][j] * p.ldc + col8;
-                if (p.Y && valid[mb][j] && st_ok) *(uint4*)(p.Y + orow[mb][j] * p.ldy + col8) = pack8(w);
-                if constexpr (EPI == 4) {
-                    if (region < 2) {
-                        float s = 0.f;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) s += w[e];
-                        const float mean = sum8(s) * (1.f / 64.f);
-                        float sq = 0.f;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) { w[e] -= mean; sq = qkln_sq(w[e], sq); }
-                        const float rstd = rsqrtf(sum8(sq) * (1.f / 64.f) + p.qn_eps);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) w[e] = qkln_affine(w[e], rstd, ga[e], be[e], post);
-                    }
-                }
-                if (EPI == 1) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) w[e] = gelu_tanh(w[e]);
-                }
+                if (p.Y && valid[mb][j]) *(uint4*)(p.Y + orow[mb][j] * p.ldy + col8) = pack8(w);
                 if (EPI == 2) {
                     float rv[8], gg[8];
                     unpack8(r8[mb][j], rv);
@@ -446,37 +310,13 @@ __device__ __forceinline__ void t8_epilogue_lds(const GemmArgs& p, f32x4 (&acc)[
 #pragma unroll
                     for (int e = 0; e < 8; ++e) w[e] *= gelu_tanh_grad(rv[e]);
                 }
-                if (valid[mb][j] && st_ok) *(uint4*)crow = pack8(w);
+                if (valid[mb][j]) *(uint4*)crow = pack8(w);
             }
             if ((EPI == 2 || EPI == 3) && mh == 0) load_rows(MB + mb, r8[mb]);       // this block's registers take block + 4
         }
     }
 }
 
-#ifdef ORV_T8_TRPROBE
-// timing probe (WRONG results; tools/t8_tr_probe.sh, profiles/r4_gemm_tn_probe.txt): what would a TN main loop (wgrad without the operand
-// transposes) cost?  Every ds_read_b128 of a fragment becomes two ds_read_b64_tr_b16 at the conflict-free addresses a row-major [8 m][64 n]
-// piece image would use, and the LDS-DMA is issued from inline asm (hipcc puts s_waitcnt vmcnt(0) in front of a transposing read that
-// follows a DMA builtin).
-typedef short t8_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) char t8_lds_char;
-__device__ __forceinline__ void t8_glds_asm(const char* sbase, unsigned voff, const void* lds_dst) {
-    unsigned keep;
-    const unsigned long long u = (unsigned long long)(uintptr_t)sbase;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi_ = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    const unsigned long long su = ((unsigned long long)hi_ << 32) | lo;
-    const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)lds_dst);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(su), "s"(d) : "memory");
-}
-__device__ __forceinline__ bf16x8 t8_tr2(t8_lds_char* a) {
-    const t8_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) t8_v4s*)(a));
-    const t8_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) t8_v4s*)(a + 512));
-    union { bf16x8 v; t8_v4s h[2]; } u;
-    u.h[0] = lo; u.h[1] = hi;
-    return u.v;
-}
-#endif
 // MB = 16-row blocks per m half of a wave: 4 = the 256-row tile (gemm_t8_kernel), 3 = a 192-row tile (gemm_t8r192_kernel, round 5: M = 3226, one
 // clip, is 17 row tiles of 192 - 510 / 255 tiles for N = 7680 / 3840 instead of 390 / 195 tiles of 256 rows on 256 CUs - and M = 6452 is 34).
 // Same streams, phases, LDS regions (an A half keeps its 16-KiB region and uses 12) and epilogues; a wave owns 96 x BN / 4, the A
@@ -490,209 +330,6 @@ template <int BN, int EPI>
 __global__ __launch_bounds__(512) void gemm_t8r192_kernel(const GemmArgs p) {
     constexpr int MB = 3;
 #include "gemm_t8_body.inc"
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// EXPERIMENT (round 4, ORV_GEMM_TILE=4,256,256 only - never chosen by the cost model): the 256 x 256 tile on FOUR waves, one per SIMD,
-// 512 registers each: a wave owns 128 x 128 (64 accumulator quads = 256 registers), so a K step of 32 needs 16 fragment reads per
-// wave instead of the 24 of two 128 x 64 waves (a third less LDS traffic), and ONE barrier per K step replaces the eight per K-tile of the
-// 8-wave ping-pong.  Nothing overlaps across waves here: a wave's own stream interleaves the MFMAs of step s with the fragment reads of step
-// s + 1 (second register set) and the LDS-DMA of step s + 4 into the region step s just left (four 32-KiB step regions: three steps = 1.5 K-tiles
-// of prefetch distance).
-// The 128 columns of a wave are two of gemm_t8_kernel's 64-column wave tiles side by side (same W-row permutation per 64 columns), so the
-// epilogues are t8's, called once per half.
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void t4_glds_asm(const char* sbase, unsigned voff, const void* lds_dst) {
-    unsigned keep;
-    const unsigned long long u = (unsigned long long)(uintptr_t)sbase;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi_ = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    const unsigned long long su = ((unsigned long long)hi_ << 32) | lo;
-    const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)lds_dst);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(su), "s"(d) : "memory");
-}
-// the accumulators are pinned to AGPRs, in place ("+a"): left to the register allocator the 64 quads were spread over both files with
-// v_accvgpr_write copies in front of most MFMAs and the DMA offsets spilled (382 TF)
-__device__ __forceinline__ void t4_mfma(f32x4& acc, const bf16x8& b, const bf16x8& a) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(b), "v"(a));
-}
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm_t4_kernel(const GemmArgs p) {
-    constexpr int BN = 256, REG = 32768, NREG = 4, SCR = NREG * REG;      // step region: A 16 blocks | B 16 blocks of 1 KiB (st_16x32)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int ns = p.K / 32;                                              // K steps per tile (K % 128 == 0)
-
-    // ---- DMA: 32 pieces per step; waves 0, 1 move the A blocks 8 w .. 8 w + 7, waves 2, 3 the B blocks ----
-    const int lsw = lane ^ ((lane >> 5) << 1);
-    const int srow = lsw >> 2, schunk = lsw & 3;
-    const bool dmaA = wave < 2;                                           // wave-uniform
-    unsigned long long gb_;
-    {
-        const unsigned long long u = (unsigned long long)(uintptr_t)(dmaA ? (const void*)p.A : (const void*)p.W);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi_ = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-        gb_ = ((unsigned long long)hi_ << 32) | lo;
-    }
-    const long ldg = dmaA ? p.lda : p.ldw;
-    unsigned off0, off1, off2, off3, off4, off5, off6, off7;              // per-lane byte offsets of this wave's eight pieces (named: an array went to scratch)
-    int s_dma = 0, t_dma = blockIdx.x;                                    // cursor of the DMA stream: (tile, step)
-#define T4_ROW(J, TM, TN)                                                                                             \
-    (dmaA ? min((TM) * 256 + (wave * 8 + (J)) * 16 + srow, p.M - 1)                                                   \
-          : (TN) * BN + (wave - 2) * 128 + (((J) >> 2) & 1) * 64 +                                                    \
-                (((J) >> 1) & 1) * 32 + 8 * (srow >> 2) + 4 * ((J) & 1) + (srow & 3))
-#define T4_OFF(J, TM, TN) (unsigned)(((long)T4_ROW(J, TM, TN) * ldg + schunk * 8) * 2)
-#define T4_SETUP(TILE)                                                                                                \
-    {                                                                                                                 \
-        int tm_, tn_;                                                                                                 \
-        tile_of_index(p, min((TILE), ntiles - 1), ntiles, tm_, tn_);                                                  \
-        off0 = T4_OFF(0, tm_, tn_); off1 = T4_OFF(1, tm_, tn_); off2 = T4_OFF(2, tm_, tn_); off3 = T4_OFF(3, tm_, tn_); \
-        off4 = T4_OFF(4, tm_, tn_); off5 = T4_OFF(5, tm_, tn_); off6 = T4_OFF(6, tm_, tn_); off7 = T4_OFF(7, tm_, tn_); \
-    }
-#define T4_ADVANCE() if (__builtin_expect(++s_dma == ns, 0)) { s_dma = 0; t_dma += gridDim.x; T4_SETUP(t_dma) }
-    T4_SETUP(t_dma)
-    const unsigned dst = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem + wave * 8192;     // LDS byte address; + region * REG + j * 1024
-#ifdef ORV_T4_NODMA     // ablation (wrong results)
-#define T4_DMA1(OFF, LDS) { asm volatile("" :: "v"(OFF), "s"(sb_), "s"(LDS)); }
-#else
-#define T4_DMA1(OFF, LDS)                                                                                             \
-    {                                                                                                                 \
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
-                     :: "v"(OFF), "s"(sb_), "s"(LDS) : "memory", "m0");                                                \
-    }
-#endif
-#define T4_ISSUE_ALL(REGION)                                                                                          \
-    {                                                                                                                 \
-        const unsigned long long sb_ = gb_ + (unsigned long long)s_dma * 64;                                          \
-        T4_DMA1(off0, dst + (REGION) * REG) T4_DMA1(off1, dst + (REGION) * REG + 1024) T4_DMA1(off2, dst + (REGION) * REG + 2048) \
-        T4_DMA1(off3, dst + (REGION) * REG + 3072) T4_DMA1(off4, dst + (REGION) * REG + 4096) T4_DMA1(off5, dst + (REGION) * REG + 5120) \
-        T4_DMA1(off6, dst + (REGION) * REG + 6144) T4_DMA1(off7, dst + (REGION) * REG + 7168)                          \
-        T4_ADVANCE()                                                                                                  \
-    }
-
-    // ---- fragments ----
-    const int fro = ((lane & 15) * 64 + (lane >> 4) * 16) ^ (((lane >> 3) & 1) << 5);
-    const char* const rdA = smem + (wr * 8) * 1024 + fro;                 // + region * REG + (mh * 4 + mb) * 1024
-    const char* const rdB = smem + 16384 + (wc * 8) * 1024 + fro;         // + region * REG + (nh * 4 + blk) * 1024
-    f32x4 acc[2][2][4][4];                                                // [nh][mh][mb][blk]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) acc[a][b][c][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    bf16x8 fa[2][8], fb[2][8];                                            // [set][block]
-    auto read_set = [&](int set, int region) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) fa[set][i] = *(const bf16x8*)(rdA + region * REG + i * 1024);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) fb[set][i] = *(const bf16x8*)(rdB + region * REG + i * 1024);
-    };
-#define T4_FENCE() __builtin_amdgcn_sched_barrier(0);
-    // one K step: [own DMA of step s + 1 landed (steps s + 2, s + 3 stay in flight) | barrier] then eight groups of { one DMA piece of
-    // step s + 4 -> REGION = s % 4 ; two fragment reads of step s + 1 ; eight MFMAs of step s }
-#ifdef ORV_T4_NOREAD
-#define T4_RD(DST, SRC) asm volatile("" : "+v"(DST));
-#else
-#define T4_RD(DST, SRC) DST = *(const bf16x8*)(SRC);
-#endif
-#define T4_MF(SET, G, I) t4_mfma(acc[(G) >> 2][(I) >> 2][(I) & 3][(G) & 3], fb[SET][G], fa[SET][I]);
-#ifdef ORV_T4_V1
-#define T4_GROUP(SET, REGION, G, OFF)                                                                                 \
-    {                                                                                                                 \
-        T4_DMA1(OFF, dst + (REGION) * REG + (G) * 1024)                                                               \
-        fa[(SET) ^ 1][G] = *(const bf16x8*)(rdA + (((REGION) + 1) & 3) * REG + (G) * 1024);                            \
-        fb[(SET) ^ 1][G] = *(const bf16x8*)(rdB + (((REGION) + 1) & 3) * REG + (G) * 1024);                            \
-        T4_MF(SET, G, 0) T4_MF(SET, G, 1) T4_MF(SET, G, 2) T4_MF(SET, G, 3) T4_MF(SET, G, 4) T4_MF(SET, G, 5) T4_MF(SET, G, 6) T4_MF(SET, G, 7) \
-        T4_FENCE()                                                                                                    \
-    }
-#else
-    // the memory instructions sit BETWEEN MFMAs (an MFMA occupies the pipe for 16 cycles: the issue slots behind it are free)
-#define T4_GROUP(SET, REGION, G, OFF)                                                                                 \
-    {                                                                                                                 \
-        T4_MF(SET, G, 0)                                                                                              \
-        T4_DMA1(OFF, dst + (REGION) * REG + (G) * 1024)                                                               \
-        T4_MF(SET, G, 1)                                                                                              \
-        T4_FENCE()                                                                                                    \
-        T4_RD(fa[(SET) ^ 1][G], rdA + (((REGION) + 1) & 3) * REG + (G) * 1024)                                        \
-        T4_FENCE()                                                                                                    \
-        T4_MF(SET, G, 2) T4_MF(SET, G, 3)                                                                             \
-        T4_FENCE()                                                                                                    \
-        T4_RD(fb[(SET) ^ 1][G], rdB + (((REGION) + 1) & 3) * REG + (G) * 1024)                                        \
-        T4_FENCE()                                                                                                    \
-        T4_MF(SET, G, 4) T4_MF(SET, G, 5) T4_MF(SET, G, 6) T4_MF(SET, G, 7)                                           \
-        T4_FENCE()                                                                                                    \
-    }
-#endif
-#define T4_STEP(SET, REGION)                                                                                          \
-    {                                                                                                                 \
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");                                                             \
-        T4_FENCE() __builtin_amdgcn_s_barrier(); T4_FENCE()                                                           \
-        const unsigned long long sb_ = gb_ + (unsigned long long)s_dma * 64;                                          \
-        T4_GROUP(SET, REGION, 0, off0) T4_GROUP(SET, REGION, 1, off1) T4_GROUP(SET, REGION, 2, off2) T4_GROUP(SET, REGION, 3, off3) \
-        T4_GROUP(SET, REGION, 4, off4) T4_GROUP(SET, REGION, 5, off5) T4_GROUP(SET, REGION, 6, off6) T4_GROUP(SET, REGION, 7, off7) \
-        T4_ADVANCE()                                                                                                  \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                            \
-        T4_FENCE()                                                                                                    \
-    }
-
-    // prologue: steps 0 .. 3 of the first tile in flight (all four regions), fragments of step 0 in set 0
-    T4_ISSUE_ALL(0) T4_ISSUE_ALL(1) T4_ISSUE_ALL(2) T4_ISSUE_ALL(3)
-    asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    T4_FENCE() __builtin_amdgcn_s_barrier(); T4_FENCE()
-    read_set(0, 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    T4_FENCE()
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        // step s: MFMAs on the fragments of region s % 4 (read during step s - 1, in set s & 1); that region is refilled with step s + 4
-        for (int s = 0; s < ns; s += 4) {
-            T4_STEP(0, 0) T4_STEP(1, 1) T4_STEP(0, 2) T4_STEP(1, 3)
-        }
-        int tm, tn;
-        tile_of_index(p, tile, ntiles, tm, tn);
-        constexpr bool lds_epi = EPI != 1 && EPI != 4;
-#pragma unroll
-        for (int nh = 0; nh < 2; ++nh) {
-            if constexpr (lds_epi) t8_epilogue_lds<BN, EPI>(p, acc[nh], tm * 256 + wr * 128, tn * BN + wc * 128 + nh * 64, lane, smem + SCR + wave * 4096);
-            else t8_epilogue<BN, EPI>(p, acc[nh], tm * 256 + wr * 128, tn * BN + wc * 128 + nh * 64, lane);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) acc[a][b][c][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#undef T4_STEP
-#undef T4_GROUP
-#undef T4_MF
-#undef T4_FENCE
-#undef T4_ISSUE_ALL
-#undef T4_DMA1
-#undef T4_ADVANCE
-#undef T4_SETUP
-#undef T4_OFF
-#undef T4_ROW
-}
-
-template <int EPI>
-int launch_t4_one(const GemmArgs& a, hipStream_t st) {
-    constexpr int smem = 4 * 32768 + 4 * 4096;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)gemm_t4_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_done = true;
-    }
-    const int grid = min(a.tiles_m * a.tiles_n, orv_num_cus());
-    hipLaunchKernelGGL((gemm_t4_kernel<EPI>), dim3(grid), dim3(256), smem, st, a);
-    return orv_check_launch("orv_gemm_bf16");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -926,15 +563,6 @@ int launch_t8_tn(const GemmArgs& a, int bn, int accumulate, hipStream_t st) {
     if (bn == 256) return accumulate ? launch_tn_one<256, 1>(a, st) : launch_tn_one<256, 0>(a, st);
     if (bn == 192) return accumulate ? launch_tn_one<192, 1>(a, st) : launch_tn_one<192, 0>(a, st);
     orv_set_error("orv_gemm_tn_bf16: no kernel for BN=%d", bn);
-    return ORV_EINVAL;
-}
-int launch_t4(const GemmArgs& a, int epi, hipStream_t st) {
-    switch (epi) {
-        case 0: return launch_t4_one<0>(a, st);
-        case 1: return launch_t4_one<1>(a, st);
-        case 2: return launch_t4_one<2>(a, st);
-    }
-    orv_set_error("orv_gemm_bf16: no t4 kernel for epilogue %d", epi);
     return ORV_EINVAL;
 }
 int launch_t8(const GemmArgs& a, int bn, int epi, hipStream_t st, int bm) {

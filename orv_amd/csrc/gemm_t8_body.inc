@@ -27,13 +27,7 @@
     // Both: every instruction has its own 32-bit per-lane byte offset (row clamp to M - 1 included, recomputed per output tile) against a
     // wave-uniform base that carries the K position (global_load_lds saddr form: no vector address arithmetic in the K loop).  Needs
     // M * lda * 2 and N * ldw * 2 < 4 GiB (the chooser checks).
-#if defined(ORV_T8_FULLLINE_ALL)
-    constexpr bool FL = true;
-#elif defined(ORV_T8_FULLLINE_NONE)
-    constexpr bool FL = false;
-#else
     constexpr bool FL = EPI == 1 || EPI == 2;
-#endif
     const int lsw = FL ? lane : lane ^ ((lane >> 5) << 1);
     const int srow = FL ? lane >> 3 : lsw >> 2;
     const int schunk = FL ? (lane & 7) ^ (srow & 6) : lsw & 3;
@@ -82,15 +76,7 @@
     if (__builtin_expect(++KC == nk, 0)) { KC = 0; TC += gridDim.x; T8_SETUP_A(OFF, H, TC) }
 #define T8_NEXT_B(OFF, KC, TC, H)                                                                                    \
     if (__builtin_expect(++KC == nk, 0)) { KC = 0; TC += gridDim.x; T8_SETUP_B(OFF, H, TC) }
-#ifdef ORV_T8_ABL_NODMA      // ablation builds (tools/t8_loop_abl.sh, wrong results): what does the K loop cost without its LDS-DMA / without its fragment reads?
-#define T8_GLDS(BASE, KC, OFF, DST) asm volatile("" :: "v"(OFF), "s"(DST))
-#else
-#ifdef ORV_T8_TRPROBE
-#define T8_GLDS(BASE, KC, OFF, DST) t8_glds_asm((const char*)(BASE) + (long)(KC) * (BK * 2), OFF, DST)
-#else
 #define T8_GLDS(BASE, KC, OFF, DST) glds16((const char*)(BASE) + (long)(KC) * (BK * 2) + (OFF), DST)
-#endif
-#endif
 #define T8_ISSUE_A0(S) { if (a_on) { T8_GLDS(p.A, kA0, oA0[0], dst2 + (S) * BUF); T8_GLDS(p.A, kA0, oA0[1], dst2 + (S) * BUF + 1024); } T8_NEXT_A(oA0, kA0, tA0, 0) }
 #define T8_ISSUE_A1(S) { if (a_on) { T8_GLDS(p.A, kA1, oA1[0], dst2 + (S) * BUF + HALF); T8_GLDS(p.A, kA1, oA1[1], dst2 + (S) * BUF + HALF + 1024); } T8_NEXT_A(oA1, kA1, tA1, 1) }
 // counted wait: N = instructions of the newest, still-allowed group of a wave that feeds both operands; a wave without A pieces has only its two
@@ -103,16 +89,11 @@
         else { T8_GLDS(p.W, kB1, oB1[0], dst1 + (S) * BUF); }                                                        \
         T8_NEXT_B(oB1, kB1, tB1, 1)                                                                                  \
     }
-#define pA0 oA0
-#define pA1 oA1
-#define pB0 oB0
-#define pB1 oB1
-    T8_SETUP_A(pA0, 0, tA0)
-    T8_SETUP_A(pA1, 1, tA1)
-    T8_SETUP_B(pB0, 0, tB0)
-    T8_SETUP_B(pB1, 1, tB1)
+    T8_SETUP_A(oA0, 0, tA0)
+    T8_SETUP_A(oA1, 1, tA1)
+    T8_SETUP_B(oB0, 0, tB0)
+    T8_SETUP_B(oB1, 1, tB1)
 
-    // ---- fragment reads: logical byte (l & 15) * 64 + (l >> 4) * 16 of a subtile, bit 5 flipped for rows 8-15
     // ---- fragment reads.  st_16x32: logical byte (l & 15) * 64 + (l >> 4) * 16 of a piece, bit 5 flipped for rows 8-15, k half 1 = + 1024 (an
     // immediate).  FL: row i = l & 15 of a block = piece i >> 3, row i & 7, k chunk (4 kh + g) ^ (i & 6): k half 1 = the same address with
     // bit 6 flipped (a second base register).
@@ -127,20 +108,6 @@
     const char* const rdB1_1 = BN == 256 ? rdB_1 + HALF : smem + 3 * HALF + wc * 2048 + fro1;
 #define T8_KH(P, KH) (FL ? ((KH) ? P##_1 : P) : P + (KH) * 1024)
 
-#ifdef ORV_T8_TRPROBE
-    t8_lds_char* trb[4];
-    t8_lds_char* trb1[4];
-    {
-        t8_lds_char* const smem3 = (t8_lds_char*)smem;
-        const int i16 = lane & 15, g4 = lane >> 4, f = ((i16 >> 3) & 1) | ((g4 & 1) << 1);
-        const int lb = g4 * 2048 + (i16 >> 2) * 128 + (i16 & 3) * 8, lb1 = g4 * 1024 + (i16 >> 2) * 128 + (i16 & 3) * 8;
-#pragma unroll
-        for (int sg = 0; sg < 4; ++sg) { trb[sg] = smem3 + (lb | ((sg ^ f) << 5)); trb1[sg] = smem3 + (lb1 | ((sg ^ f) << 5)); }
-    }
-#endif
-#if defined(ORV_T8_TRPROBE) || defined(ORV_T8_SCHED2) || defined(ORV_T8_SCHED3)
-    static_assert(MB == 4, "the probe / experiment schedules exist for the 256-row tile only");
-#endif
     f32x4 acc[2][MB][NBW];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -150,75 +117,23 @@
             for (int c = 0; c < NBW; ++c) acc[a][b][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 fa[2][MB][2], fb[NBW][2];
 
-#ifdef ORV_T8_ABL_NOREAD
-#define T8_READ_A(MH, S)                                                                                             \
-    _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                 \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh) asm volatile("" : "+v"(fa[MH][mb][kh]));
-#elif defined(ORV_T8_ABL_NOA1)
-#define T8_READ_A(MH, S)                                                                                             \
-    _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                 \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
-            fa[MH][mb][kh] = (MH) ? fa[0][mb][kh] : *(const bf16x8*)(T8_KH(rdA, kh) + (S) * BUF + (MH) * HALF + mb * 2048);
-#elif defined(ORV_T8_TRPROBE)
-#define T8_READ_A(MH, S)                                                                                             \
-    _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                 \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
-            fa[MH][mb][kh] = t8_tr2(trb[mb] + (S) * BUF + (MH) * HALF + wr * 1024 + kh * 8192);
-#else
 #define T8_READ_A(MH, S)                                                                                             \
     _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                                 \
         _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
             fa[MH][mb][kh] = *(const bf16x8*)(T8_KH(rdA, kh) + (S) * BUF + (MH) * HALF + mb * 2048);
-#endif
-#ifdef ORV_T8_ABL_NOREAD
-#define T8_READ_B01(S)                                                                                               \
-    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                    \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh) asm volatile("" : "+v"(fb[t][kh]));
-#elif defined(ORV_T8_TRPROBE)
-#define T8_READ_B01(S)                                                                                               \
-    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                    \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
-            fb[t][kh] = t8_tr2(trb[2 * (wc & 1) + t] + (S) * BUF + 2 * HALF + (wc >> 1) * 1024 + kh * 8192);
-#else
 #define T8_READ_B01(S)                                                                                               \
     _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                    \
         _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
             fb[t][kh] = *(const bf16x8*)(T8_KH(rdB, kh) + (S) * BUF + t * 2048);
-#endif
-#if defined(ORV_T8_ABL_NOREAD)
-#define T8_READ_B23(S)                                                                                               \
-    _Pragma("unroll") for (int t = 0; t < NBW - 2; ++t)                                                              \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh) asm volatile("" : "+v"(fb[2 + t][kh]));
-#elif defined(ORV_T8_ABL_NOB23)      // ablation builds (tools/t8_lds_abl.sh, wrong results): how much do the fragment reads cost?
-#define T8_READ_B23(S)                                                                                               \
-    _Pragma("unroll") for (int t = 0; t < NBW - 2; ++t)                                                              \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
-            fb[2 + t][kh] = fb[t][kh];
-#elif defined(ORV_T8_TRPROBE)
-#define T8_READ_B23(S)                                                                                               \
-    _Pragma("unroll") for (int t = 0; t < NBW - 2; ++t)                                                              \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
-            fb[2 + t][kh] = BN == 256 ? t8_tr2(trb[2 * (wc & 1) + t] + (S) * BUF + 3 * HALF + (wc >> 1) * 1024 + kh * 8192)                  \
-                                      : t8_tr2(trb1[wc] + (S) * BUF + 3 * HALF + kh * 4096);
-#else
 #define T8_READ_B23(S)                                                                                               \
     _Pragma("unroll") for (int t = 0; t < NBW - 2; ++t)                                                              \
         _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
             fb[2 + t][kh] = *(const bf16x8*)(T8_KH(rdB1, kh) + (S) * BUF + t * 2048);
-#endif
-    // (m half MH) x (blocks B0 .. B0 + NBK - 1), both k halves
-#ifdef ORV_T8_ABL_NOMFMA
-#define T8_MFMA(MH, B0, NBK)                                                                                         \
-    _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                                 \
-        _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                             \
-            _Pragma("unroll") for (int t = 0; t < (NBK); ++t) asm volatile("" : "+v"(acc[MH][mb][(B0) + t]) : "v"(fb[(B0) + t][kh]), "v"(fa[MH][mb][kh]));
-#else
 #define T8_MFMA(MH, B0, NBK)                                                                                         \
     _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                                 \
         _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                                                             \
             _Pragma("unroll") for (int t = 0; t < (NBK); ++t)                                                        \
                 acc[MH][mb][(B0) + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[(B0) + t][kh], fa[MH][mb][kh], acc[MH][mb][(B0) + t], 0, 0, 0);
-#endif
 #define T8_BAR()                                                                                                     \
     __builtin_amdgcn_sched_barrier(0);                                                                               \
     __builtin_amdgcn_s_barrier();                                                                                    \
@@ -273,137 +188,15 @@
         T8_BAR() T8_PRIO1() T8_MFMA(1, 0, 2) T8_PRIO0() T8_BAR()                                                     \
     }
 
-    // ---- experiment (-DORV_T8_SCHED2, tools/t8_sched_ab.sh): TWO phases of 32 (24) MFMAs per K-tile instead of four (three) of 16: half as
-    // many barriers per MFMA, load segments of 20 + 4 (14 + 8) fragment reads that are closer to the MFMA segments in length.  The
-    // fragment reads are retired BEFORE a phase's first barrier (the DMA that restages a region is issued one phase after its last
-    // reader passed that barrier), one counted vmcnt per phase.
-    //   BN = 256: P1 reads A0 A1 B01, issues B1 (region 1) of K-tile + 1, MFMA (m0 m1) x n01 | P2 reads B23, issues A0 A1 B0 of K-tile + 2,
-    //             MFMA (m0 m1) x n23; vmcnt(8) in both.
-    //   BN = 192: P1 reads A0 B012, issues A1 of K-tile + 1, MFMA m0 x n012 | P2 reads A1, issues A0 B0 B1 of K-tile + 2, MFMA m1 x n012;
-    //             vmcnt(7) in both.
-#define T8_LGKM0_PRE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define T8_KTILE2_256(S)                                                                                             \
-    {                                                                                                                \
-        T8_READ_B01(S)                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_READ_A(0, S)                                                                                              \
-        T8_READ_A(1, S)                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_B1((S) ^ 1)                                                                                         \
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                                             \
-        T8_LGKM0_PRE()                                                                                               \
-        T8_BAR() T8_PRIO1() T8_MFMA(0, 0, 2) T8_MFMA(1, 0, 2) T8_PRIO0() T8_BAR()                                    \
-        T8_READ_B23(S)                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_A0(S)                                                                                               \
-        T8_ISSUE_A1(S)                                                                                               \
-        T8_ISSUE_B0(S)                                                                                               \
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                                             \
-        T8_LGKM0_PRE()                                                                                               \
-        T8_BAR() T8_PRIO1() T8_MFMA(0, 2, 2) T8_MFMA(1, 2, 2) T8_PRIO0() T8_BAR()                                    \
-    }
-#define T8_KTILE2_192(S)                                                                                             \
-    {                                                                                                                \
-        T8_READ_B01(S)                                                                                               \
-        T8_READ_B23(S)                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_READ_A(0, S)                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_A1((S) ^ 1)                                                                                         \
-        asm volatile("s_waitcnt vmcnt(7)" ::: "memory");                                                             \
-        T8_LGKM0_PRE()                                                                                               \
-        T8_BAR() T8_PRIO1() T8_MFMA(0, 0, 3) T8_PRIO0() T8_BAR()                                                     \
-        T8_READ_A(1, S)                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_A0(S)                                                                                               \
-        T8_ISSUE_B0(S)                                                                                               \
-        T8_ISSUE_B1(S)                                                                                               \
-        asm volatile("s_waitcnt vmcnt(7)" ::: "memory");                                                             \
-        T8_LGKM0_PRE()                                                                                               \
-        T8_BAR() T8_PRIO1() T8_MFMA(1, 0, 3) T8_PRIO0() T8_BAR()                                                     \
-    }
-
-    // ---- SCHED3 (-DORV_T8_SCHED3, BN = 256; tools/t8_sched3_ab.sh): the four phases with BALANCED load segments.  Ablation of the shipped loop
-    // (profiles/r4_gemm_loop_ablation.txt): MFMAs + barriers alone 0.518 ms, LDS-DMA + fragment reads + barriers alone 0.544 ms, together 0.777 ms
-    // (8192^3) - the two sides are equal and overlap badly, because the fragment reads are 12 / 8 / 4 / 0 per phase: P1's load segment (12 reads + 2
-    // DMA instructions = 320 LDS cycles) outlasts its partner's 256 MFMA cycles while P4's (128) idles.  Here B01 (dead after P2) and the first block
-    // of A1 (dead after P3) of the NEXT K-tile are read in P4: reads 8 / 6 / 4 / 6, DMA 2 / 2 / 2 / 2 (B0, A0, A1, B1 of K-tile + 2: every stream two
-    // K-tiles ahead), all four load segments <= 256 LDS cycles.  Fragment reads are retired BEFORE a phase's first barrier, so a region is restaged
-    // one interval after its last reader; one vmcnt(6) per K-tile in P3 (retires K-tile + 1 completely: P4 reads it).  The tile's first K-tile
-    // reads B01 / A1 head itself in P1 (T8C_KTILE_FIRST) and issues its P1 DMA in P2 (the second half reads B01 one interval later).
-#define T8_READ_A1_HEAD(S)                                                                                           \
-    _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                                 \
-        fa[1][0][kh] = *(const bf16x8*)(T8_KH(rdA, kh) + (S) * BUF + HALF);
-#define T8_READ_A1_REST(S)                                                                                           \
-    _Pragma("unroll") for (int mb = 1; mb < 4; ++mb)                                                                 \
-        _Pragma("unroll") for (int kh = 0; kh < 2; ++kh)                                                             \
-            fa[1][mb][kh] = *(const bf16x8*)(T8_KH(rdA, kh) + (S) * BUF + HALF + mb * 2048);
-#define T8C_PRE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define T8C_TAIL(S)                                                                                                  \
-        T8_READ_B23(S)                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_A1(S)                                                                                               \
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                                             \
-        T8C_PRE()                                                                                                    \
-        T8_BAR() T8_PRIO1() T8_MFMA(1, 2, 2) T8_PRIO0() T8_BAR()                                                     \
-        T8_READ_B01((S) ^ 1)                                                                                         \
-        T8_READ_A1_HEAD((S) ^ 1)                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_B1(S)                                                                                               \
-        T8C_PRE()                                                                                                    \
-        T8_BAR() T8_PRIO1() T8_MFMA(0, 2, 2) T8_PRIO0() T8_BAR()
-#define T8C_KTILE(S)                                                                                                 \
-    {                                                                                                                \
-        T8_READ_A(0, S)                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_B0(S)                                                                                               \
-        T8C_PRE()                                                                                                    \
-        T8_BAR() T8_PRIO1() T8_MFMA(0, 0, 2) T8_PRIO0() T8_BAR()                                                     \
-        T8_READ_A1_REST(S)                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_A0(S)                                                                                               \
-        T8C_PRE()                                                                                                    \
-        T8_BAR() T8_PRIO1() T8_MFMA(1, 0, 2) T8_PRIO0() T8_BAR()                                                     \
-        T8C_TAIL(S)                                                                                                  \
-    }
-#define T8C_KTILE_FIRST(S)                                                                                           \
-    {                                                                                                                \
-        T8_READ_B01(S)                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_READ_A(0, S)                                                                                              \
-        T8_READ_A1_HEAD(S)                                                                                           \
-        T8C_PRE()                                                                                                    \
-        T8_BAR() T8_PRIO1() T8_MFMA(0, 0, 2) T8_PRIO0() T8_BAR()                                                     \
-        T8_READ_A1_REST(S)                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                                           \
-        T8_ISSUE_B0(S)                                                                                               \
-        T8_ISSUE_A0(S)                                                                                               \
-        T8C_PRE()                                                                                                    \
-        T8_BAR() T8_PRIO1() T8_MFMA(1, 0, 2) T8_PRIO0() T8_BAR()                                                     \
-        T8C_TAIL(S)                                                                                                  \
-    }
-
     // prologue: K-tile 0 complete into buffer 0, then the pieces of K-tile 1 the steady state would have issued by now
     if constexpr (BN == 256) {
-#ifdef ORV_T8_SCHED3
-        T8_ISSUE_A0(0) T8_ISSUE_B0(0) T8_ISSUE_A1(0) T8_ISSUE_B1(0)
-        T8_ISSUE_B0(1) T8_ISSUE_A0(1) T8_ISSUE_A1(1) T8_ISSUE_B1(1)
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#else
         T8_ISSUE_A0(0) T8_ISSUE_B0(0) T8_ISSUE_A1(0) T8_ISSUE_B1(0)
         T8_ISSUE_B0(1) T8_ISSUE_A0(1) T8_ISSUE_A1(1)
         T8_VMCNT(6)
-#endif
     } else {
-#ifdef ORV_T8_SCHED2
-        T8_ISSUE_A0(0) T8_ISSUE_B0(0) T8_ISSUE_A1(0) T8_ISSUE_B1(0)
-        T8_ISSUE_A0(1) T8_ISSUE_B0(1) T8_ISSUE_B1(1)
-        asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-#else
         T8_ISSUE_A0(0) T8_ISSUE_B0(0) T8_ISSUE_A1(0) T8_ISSUE_B1(0)
         T8_ISSUE_B0(1) T8_ISSUE_A0(1)
         T8_VMCNT(4)
-#endif
     }
     if (p.stagger_groups > 1) {
         // the prologue's DMA is in flight; this workgroup's group waits its share of the stagger before the first K-tile
@@ -413,69 +206,23 @@
     }
     T8_BAR()
 
-#ifdef ORV_T8_TRACE   // tools/trace_t8.cpp (EPI 0 / 1 builds only: R doubles as the trace buffer): wall-clock stamps (10 ns) of waves 0 and 4 of
-    // workgroups 0, 8 and 100: [loop start, after K-tiles 0-1, after K-tiles 2-3, loop end, epilogue start, epilogue end (stores issued),
-    // (ORV_T8_TRACE == 2: + after s_waitcnt vmcnt(0), i.e. the stores have drained)] for their first 8 tiles
-    int trace_i = 0;
-    const int trace_w = blockIdx.x == 0 ? 0 : (blockIdx.x == 8 ? 1 : (blockIdx.x == 100 ? 2 : -1));
-#define T8_STAMP(SLOT)                                                                                               \
-    if (trace_w >= 0 && (wave & 3) == 0 && lane == 0 && trace_i < 8)                                                 \
-        ((unsigned long long*)p.R)[((trace_w * 2 + wr) * 8 + trace_i) * 8 + (SLOT)] = wall_clock64();
-#else
-#define T8_STAMP(SLOT)
-#endif
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         if (wr == 1) { T8_BAR() }             // the second half of the workgroup runs one barrier behind ...
-        T8_STAMP(0)
-#ifdef ORV_T8_SCHED3
-        if constexpr (BN == 256) { T8C_KTILE_FIRST(0) T8C_KTILE(1) }
-#endif
-        for (int kt = (BN == 256 && T8_SCHED3_ON) ? 2 : 0; kt < nk; kt += 2) {
-#ifdef ORV_T8_SCHED3
-            if constexpr (BN == 256) { T8C_KTILE(0) T8C_KTILE(1) }
-            else { T8_KTILE_192(0) T8_KTILE_192(1) }
-#elif defined(ORV_T8_SCHED2)
-            if constexpr (BN == 256) { T8_KTILE2_256(0) T8_KTILE2_256(1) }
-            else { T8_KTILE2_192(0) T8_KTILE2_192(1) }
-#else
+        for (int kt = 0; kt < nk; kt += 2) {
             if constexpr (BN == 256) { T8_KTILE_256(0) T8_KTILE_256(1) }
             else { T8_KTILE_192(0) T8_KTILE_192(1) }
-#endif
-#ifdef ORV_T8_TRACE
-            if (kt == 0) { T8_STAMP(1) }
-            if (kt == 2) { T8_STAMP(2) }
-#endif
         }
-        T8_STAMP(3)
         if (wr == 0) { T8_BAR() }             // ... and both halves run their epilogues side by side
-        T8_STAMP(4)
         int tm, tn;
         tile_of_index(p, tile, ntiles, tm, tn);
-#ifdef ORV_T8_ABL_NOEPI      // ablation build: no epilogue at all (the accumulators stay live through the never-taken call)
-        if (p.M < 0)
-#endif
         // which epilogue: the LDS-transposed one wins where row operands are LOADED (gated residual: FFN2 -4.5 %, out-projection
         // -2...4 %) and is level or better for the plain one; the GELU epilogue is bound by its two transcendentals per element and
         // pays the LDS round trip on top (+1...2 %), the qk-LayerNorm epilogue pays it and the 8-lane DPP reductions (+2.6 % on the
-        // QKV pair in the model): those two keep the register-layout form
-        // (profiles/r4_gemm_epilogue_ablation.txt).  -DORV_T8_EPI_DIRECT / -DORV_T8_EPI_LDS force one form (A/B builds).
-#if defined(ORV_T8_EPI_DIRECT)
-        constexpr bool lds_epi = false;
-#elif defined(ORV_T8_EPI_LDS)
-        constexpr bool lds_epi = true;
-#else
+        // QKV pair in the model): those two keep the register-layout form (profiles/r4_gemm_epilogue_ablation.txt).  Each form
+        // holds the code of its own epilogues only (static_assert in both).
         constexpr bool lds_epi = EPI != 1 && EPI != 4;
-#endif
         if constexpr (lds_epi) t8_epilogue_lds<BN, EPI, MB>(p, acc, tm * BM + wr * (BM / 2), tn * BN + wc * (BN / 4), lane, smem + SCR + wave * 4096);
         else t8_epilogue<BN, EPI, MB>(p, acc, tm * BM + wr * (BM / 2), tn * BN + wc * (BN / 4), lane);
-        T8_STAMP(5)
-#ifdef ORV_T8_TRACE
-#if ORV_T8_TRACE == 2
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        T8_STAMP(6)
-#endif
-        ++trace_i;
-#endif
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll

@@ -1,6 +1,6 @@
 #!/bin/bash
 # build gemm_d8 variants into tools/bin/dv_<name>/liborv_mi355.so (compile-time switches)
-# usage: VARIANTS="noread:-DORV_D8_ABL_NOREAD nodma:-DORV_D8_ABL_NODMA" bash tools/d8_variants.sh
+# usage: VARIANTS="cbp4:-DORV_D8_CBP256=4 cbp2:-DORV_D8_CBP192=2" bash tools/d8_variants.sh
 cd /root/repo/orv_amd/csrc
 for v in $VARIANTS; do
   name=${v%%:*}; flags=$(echo ${v#*:} | tr ',' ' ')

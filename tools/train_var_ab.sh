@@ -1,5 +1,5 @@
 #!/bin/bash
-# training-step A/B of library variants (tools/bin/gv_<name>) against the in-tree build, same box, interleaved: bash tools/train_var_ab.sh head flall flnone base
+# training-step A/B of library variants (tools/bin/gv_<name>) against the in-tree build, same box, interleaved: bash tools/train_var_ab.sh name1 name2 base
 cd /root/repo; mkdir -p gpurun_out
 {
 for r in 1 2; do for n in "$@"; do
