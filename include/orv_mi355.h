@@ -336,6 +336,40 @@ int orv_prodigy_recurrence(double* state, const double* partials, long nchunks, 
 int orv_prodigy_update(void* p, void* lo, const float* m, const float* v, long n, const long* seg_start,
                        const unsigned char* seg_active, int nseg, const double* state, float eps, float weight_decay, int decouple,
                        void* stream);
+/* Fused CAME (FusedCAME): Adam with a factored second moment and a confidence term, on the flat layout of
+ * orv_adamw_flat_ex.  Operation order, g the gradient times *clip_coef (NULL: 1), every state value fp32 and zero at the start:
+ *      q = g g + eps1
+ *      segment of shape [B, R, C] (R > 0), per matrix:   r = b2 r + (1-b2) mean_j q ;  c = b2 c + (1-b2) mean_i q
+ *                                                        u = (g rsqrt(r_i / mean_i r)) rsqrt(c_j)
+ *      unfactored segment (R == 0):                      v = b2 v + (1-b2) q ;  u = g rsqrt(v)
+ *      k = max(1, sqrt(mean of u u over the segment) / clip_threshold) ;  u = u / k
+ *      m = b1 m + (1-b1) u ;  s = (u - m)^2 + eps2                                      (the new m)
+ *      factored:   res_r = b3 res_r + (1-b3) mean_j s ;  res_c = b3 res_c + (1-b3) mean_i s
+ *                  out = (m rsqrt(res_r_i / mean_i res_r)) rsqrt(res_c_j) ;      unfactored:   out = m
+ *      w = w - (weight_decay lr) w  (weight_decay != 0) ;  w = w - lr out
+ * w and its store are those of orv_adamw_flat_ex: mode 0 the bf16 weight rounded to nearest-even, mode 1 the split fp32 master p + lo.
+ * geom is a DEVICE table of 12 int64 per segment: B, R, C, first tile, first matrix, offset of the segment in r / res_r, in c / res_c, in v
+ * (a multiple of 2048), in the row partial sums, in the column partial sums, element count, 0.  A factored segment owns B matrices, B R
+ * rows, B C columns, B ceil(R / 64) ceil(C / 256) tiles, B R ceil(C / 256) row partials and B C ceil(R / 64) column partials; an unfactored
+ * one ceil(numel / 2048) tiles and as many elements of v, padded to 2048; n_tiles .. n_colp are the totals.  scratch (fp32, contents
+ * meaningless between steps, every value read in a step is written in it first) holds at least
+ * n_rowp + n_colp + n_tiles + n_rows + n_cols + 2 nseg values; its last 2 nseg are (k, RMS of u) per segment after a step.
+ * One step is the launches which = 0 .. 6 in order on one stream (orv_came_step issues them all): no host read, no atomics, every sum in a
+ * fixed order.  Inactive segments and padding keep every byte.  A null descriptor or buffer, n % 2048 != 0, a mode other than 0 / 1,
+ * eps1 <= 0, clip_threshold <= 0 or a scratch that is too small return non-zero with an orv_last_error message before anything is launched. */
+typedef struct {
+    void* p; void* lo; const void* g; float* m;                  /* bf16[n], int16[n] (mode 1) or NULL, bf16[>= n], fp32[n] */
+    float* r; float* c; float* res_r; float* res_c; float* v;    /* fp32[n_rows], [n_cols], [n_rows], [n_cols], [n_v] */
+    long n, n_rows, n_cols, n_v;
+    const long* seg_start; const unsigned char* seg_active; int nseg;
+    const long* geom; long n_tiles, n_mats, n_rowp, n_colp;
+    float* scratch; long n_scratch;
+    const float* clip_coef;
+    float lr, beta1, beta2, beta3, eps1, eps2, clip_threshold, weight_decay;
+    int mode;
+} orv_came_t;
+int orv_came_launch(const orv_came_t* d, int which, void* stream);
+int orv_came_step(const orv_came_t* d, void* stream);
 /* dst_ptr[s][j] = bf16(src[src_off[s] + j]), j < len[s], for nseg segments (src_off / dst_ptr / len are DEVICE arrays; dst_ptr holds
  * device addresses of bf16 storage; max_len = max len[s]): the small fp32-accumulated parameter gradients go from the backward's
  * accumulator arena into the fused optimizer's flat gradient buffer in one launch (the reference leaves this to autograd's

@@ -39,6 +39,16 @@ class Frames(Structure):
     _fields_ = [("data", c_void_p), ("kind", c_int), ("h", c_int), ("w", c_int), ("extent", c_long), ("offset", c_long), ("stride", c_long * 4)]
 
 
+class Came(Structure):      # orv_came_t
+    _fields_ = ([(n, c_void_p) for n in ("p", "lo", "g", "m", "r", "c", "res_r", "res_c", "v")]
+                + [(n, c_long) for n in ("n", "n_rows", "n_cols", "n_v")]
+                + [("seg_start", c_void_p), ("seg_active", c_void_p), ("nseg", c_int), ("geom", c_void_p)]
+                + [(n, c_long) for n in ("n_tiles", "n_mats", "n_rowp", "n_colp")]
+                + [("scratch", c_void_p), ("n_scratch", c_long), ("clip_coef", c_void_p)]
+                + [(n, c_float) for n in ("lr", "beta1", "beta2", "beta3", "eps1", "eps2", "clip_threshold", "weight_decay")]
+                + [("mode", c_int)])
+
+
 # name -> (restype, argtypes); every symbol include/orv_mi355.h declares
 SIGNATURES = {
     "orv_version": (c_int, []),
@@ -122,6 +132,8 @@ SIGNATURES = {
                                        c_void_p]),
     "orv_prodigy_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float,
                                    c_int, c_void_p]),
+    "orv_came_launch": (c_int, [POINTER(Came), c_int, c_void_p]),
+    "orv_came_step": (c_int, [POINTER(Came), c_void_p]),
     "orv_scatter_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "orv_sumsq": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "orv_head_transpose": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -604,7 +604,88 @@ def prodigy_update(p, lo, m, v, seg_start, seg_active, state, eps, weight_decay=
                                    float(eps), float(weight_decay), int(bool(decouple)), _stream()), "orv_prodigy_update")
 
 
-STATE8_FORMATS = {"m": 0, "v": 1}          # first moment: e4m3fn, second moment: e5m2 (orv_amd/csrc/optim_s8.hip)
+CAME_LAUNCHES = ("q_sums", "statistics", "usq_sums", "k", "m_and_s_sums", "confidence", "weights")     # `which` of orv_came_launch
+CAME_TILE = (64, 256)                    # rows x columns of one workgroup's tile of a factored matrix (orv_amd/csrc/optim_came.hip)
+CAME_GEOM = ("B", "R", "C", "tile0", "mat0", "row0", "col0", "v0", "rowp0", "colp0", "numel", "pad")
+
+
+def came_geometry(shapes):
+    """The geometry table of ``orv_came_*`` for parameters of these shapes, one flat segment each (host arithmetic only): a shape of two or
+    more dimensions is ``B = prod(shape[:-2])`` matrices of ``R x C`` with row / column statistics, anything else is unfactored (``R = 0``)
+    and keeps one value of ``v`` per element, padded to 2048.  -> dict: ``table`` (rows of ``CAME_GEOM``), the totals ``n_tiles``,
+    ``n_mats``, ``n_rows``, ``n_cols``, ``n_v``, ``n_rowp``, ``n_colp`` and ``n_scratch``, the fp32 values of scratch one step needs."""
+    tr, tc = CAME_TILE
+    t = dict(n_tiles=0, n_mats=0, n_rows=0, n_cols=0, n_v=0, n_rowp=0, n_colp=0)
+    table = []
+    for shape in shapes:
+        shape = tuple(int(d) for d in shape)
+        numel = 1
+        for d in shape:
+            numel *= d
+        if numel <= 0:
+            raise ValueError(f"orv_amd.ops.came_geometry: a parameter of shape {shape} has no elements")
+        if len(shape) >= 2:
+            R, C = shape[-2:]
+            B = numel // (R * C)
+            nrt, nct = -(-R // tr), -(-C // tc)
+            own = dict(n_tiles=B * nrt * nct, n_mats=B, n_rows=B * R, n_cols=B * C, n_v=0, n_rowp=B * R * nct, n_colp=B * C * nrt)
+        else:
+            B, R, C = 1, 0, 0
+            chunks = -(-numel // 2048)
+            own = dict(n_tiles=chunks, n_mats=0, n_rows=0, n_cols=0, n_v=chunks * 2048, n_rowp=0, n_colp=0)
+        table.append([B, R, C, t["n_tiles"], t["n_mats"], t["n_rows"], t["n_cols"], t["n_v"], t["n_rowp"], t["n_colp"], numel, 0])
+        for k, x in own.items():
+            t[k] += x
+    t["n_scratch"] = t["n_rowp"] + t["n_colp"] + t["n_tiles"] + t["n_rows"] + t["n_cols"] + 2 * len(table)
+    t["table"] = table
+    return t
+
+
+def came_step(p, g, m, stats, seg_start, seg_active, geom, sizes, scratch, lr, betas, eps=(1e-30, 1e-16), clip_threshold=1.0,
+              weight_decay=0.0, clip_coef=None, lo=None, mode=0, which=None):
+    """One fused CAME step (``orv_came_step``: seven stream-ordered launches) on the flat layout of ``adamw_flat_ex``, or
+    the single launch ``which`` (an index or a name of ``CAME_LAUNCHES``; ``orv_came_launch``).  ``stats``: dict of the fp32 statistics
+    ``r``, ``c``, ``res_r``, ``res_c`` (``sizes["n_rows"]`` / ``["n_cols"]`` values) and ``v`` (``sizes["n_v"]``; an entry of size 0 may be
+    None); ``geom``: the int64 device copy of ``came_geometry(...)["table"]``, ``sizes`` that dict; ``scratch``: fp32, at least
+    ``sizes["n_scratch"]`` values; ``mode`` 0 (bf16 weights, nearest-even) or 1 (split fp32 master, needs ``lo``)."""
+    from ._lib import Came
+    mode = ADAMW_MODES.get(mode, mode)
+    _need(p, BF16, "p"), _need(g, BF16, "g"), _need(m, torch.float32, "m"), _need(scratch, torch.float32, "scratch")
+    _need(seg_start, torch.int64, "seg_start"), _need(seg_active, torch.uint8, "seg_active"), _need(geom, torch.int64, "geom")
+    named = [("p", p), ("g", g), ("m", m), ("scratch", scratch), ("seg_start", seg_start), ("seg_active", seg_active), ("geom", geom)]
+    if lo is not None:
+        named.append(("lo", _need(lo, torch.int16, "lo")))
+    if clip_coef is not None:
+        named.append(("clip_coef", _need(clip_coef, torch.float32, "clip_coef")))
+    want = {"r": sizes["n_rows"], "c": sizes["n_cols"], "res_r": sizes["n_rows"], "res_c": sizes["n_cols"], "v": sizes["n_v"]}
+    for k, cnt in want.items():
+        s = stats.get(k)
+        if s is None and cnt == 0:
+            continue
+        if s is None or _need(s, torch.float32, k).numel() != cnt:
+            raise RuntimeError(f"orv_amd.ops: came_step statistic `{k}` must hold {cnt} fp32 values")
+        named.append((k, s))
+    for name, t in named:
+        if not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+    nseg, n = seg_active.numel(), p.numel()
+    if (g.numel() < n or m.numel() != n or seg_start.numel() != nseg + 1 or geom.numel() != nseg * len(CAME_GEOM)
+            or len(sizes["table"]) != nseg or (lo is not None and lo.numel() != n)):
+        raise RuntimeError("orv_amd.ops: came_step buffers do not share one flat layout")
+    d = Came(p=_p(p), lo=_p(lo), g=_p(g), m=_p(m), r=_p(stats.get("r")), c=_p(stats.get("c")), res_r=_p(stats.get("res_r")),
+             res_c=_p(stats.get("res_c")), v=_p(stats.get("v")), n=n, n_rows=sizes["n_rows"], n_cols=sizes["n_cols"], n_v=sizes["n_v"],
+             seg_start=_p(seg_start), seg_active=_p(seg_active), nseg=nseg, geom=_p(geom), n_tiles=sizes["n_tiles"], n_mats=sizes["n_mats"],
+             n_rowp=sizes["n_rowp"], n_colp=sizes["n_colp"], scratch=_p(scratch), n_scratch=scratch.numel(), clip_coef=_p(clip_coef),
+             lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), beta3=float(betas[2]), eps1=float(eps[0]), eps2=float(eps[1]),
+             clip_threshold=float(clip_threshold), weight_decay=float(weight_decay), mode=int(mode))
+    if which is None:
+        check(lib().orv_came_step(d, _stream()), "orv_came_step")
+    else:
+        which = CAME_LAUNCHES.index(which) if isinstance(which, str) else int(which)
+        check(lib().orv_came_launch(d, which, _stream()), "orv_came_launch")
+
+
+STATE8_FORMATS = {"m": 0, "v": 1}         # first moment: e4m3fn, second moment: e5m2 (orv_amd/csrc/optim_s8.hip)
 
 
 def _need_state8(q, exps, what):

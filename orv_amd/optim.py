@@ -24,7 +24,8 @@ element - rounded stochastically with offsets from the same kind of hash (``seed
 identical state.  It is orthogonal to ``param_precision``; the format is defined in ``orv_amd/csrc/optim_s8.hip``.
 
 ``FusedProdigy`` is the learning-rate-free Prodigy update on the same storage, ``get_optimizer`` the reference's factory
-(``train.optimizer.type: adamw | adam | prodigy``) over both classes."""
+(``train.optimizer.type: adamw | adam | prodigy``) over both classes.  ``FusedCAME`` is the reference's fourth choice,
+CAME: one fp32 moment per element and a factored second moment, constructed directly."""
 from __future__ import annotations
 
 from typing import Iterable, List, Optional
@@ -43,6 +44,8 @@ _AR_CHUNK = 128 * 1024 * 1024   # bf16 elements per all-reduce call (256 MB: lar
 
 class FusedAdamW:
     _checkpoint_kind = "adamw"
+    _element_moments = ("m", "v")       # the fp32 per-element moment buffers ``_build`` allocates (FusedCAME keeps no element-sized v)
+    _moment_keys = {"m": "exp_avg", "v": "exp_avg_sq"}      # their names in a checkpoint
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr=1e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-3,
                  max_grad_norm: float = 1.0, param_precision: str = "bf16", seed: int = 0, state_precision: str = "fp32"):
@@ -103,7 +106,7 @@ class FusedAdamW:
             z8 = lambda n: torch.zeros(n, dtype=torch.uint8, device=dev)
             self._flat.update(m8=z8(total), v8=z8(total), m_exp=z8(total // _BLOCK), v_exp=z8(total // _BLOCK))
         else:
-            self._flat.update(m=torch.zeros(total, dtype=torch.float32, device=dev), v=torch.zeros(total, dtype=torch.float32, device=dev))
+            self._flat.update({b: torch.zeros(total, dtype=torch.float32, device=dev) for b in self._element_moments})
         if self.param_precision == "split_fp32":
             # low halves of the fp32 masters, same segment layout as `p`; zeros: the master is the current bf16 value exactly
             lo = torch.zeros(total, dtype=torch.int16, device=dev)
@@ -319,9 +322,9 @@ class FusedAdamW:
         if self.state_precision == "fp8":
             m, v = self._dequantized(f["m8"], f["m_exp"], "m"), self._dequantized(f["v8"], f["v_exp"], "v")
         else:
-            m, v = f["m"], f["v"]
+            m, v = f["m"], f.get("v")
         cut = lambda x: [x[o:o + p.numel()].view(p.shape).clone() for p, o in zip(self.params, f["offs"])]
-        return cut(m), cut(v)
+        return cut(m), None if v is None else cut(v)
 
     # ---- checkpointing (torch.optim-like) ----
     def state_dict(self):
@@ -330,7 +333,7 @@ class FusedAdamW:
         layout = [int(p.numel()) for p in self.params]
         mode = {"param_precision": self.param_precision, "state_precision": self.state_precision, "seed": self.seed}
         fp8 = self.state_precision == "fp8"
-        names = {"exp_avg8": "m8", "exp_avg_sq8": "v8", "exp_avg_exp": "m_exp", "exp_avg_sq_exp": "v_exp"} if fp8 else {"exp_avg": "m", "exp_avg_sq": "v"}
+        names = {"exp_avg8": "m8", "exp_avg_sq8": "v8", "exp_avg_exp": "m_exp", "exp_avg_sq_exp": "v_exp"} if fp8 else {self._moment_keys[b]: b for b in self._element_moments}
         if self._flat is None:
             return {"step": self.step_count, **{k: None for k in names}, "numels": layout, **mode}
         sd = {"step": self.step_count, **{k: self._flat[b] for k, b in names.items()}, "numels": layout,
@@ -343,7 +346,7 @@ class FusedAdamW:
     def load_state_dict(self, sd):
         if sd.get("optimizer") not in (None, self._checkpoint_kind):        # FusedAdamW's own checkpoints carry no such key
             raise ValueError(f"{type(self).__name__}.load_state_dict: the checkpoint was written by the {sd['optimizer']!r} optimizer; its moments "
-                             "have another meaning (Prodigy's carry a factor d) and are not taken over")
+                             "have another meaning (Prodigy's carry a factor d, CAME's second moment is factored) and are not taken over")
         layout = [int(p.numel()) for p in self.params]
         if sd.get("numels") is not None and list(sd["numels"]) != layout:
             if sorted(sd["numels"]) == sorted(layout):
@@ -374,13 +377,13 @@ class FusedAdamW:
                 self._build()
             f = self._flat
             total = f["p"].numel()
-            keys = ("exp_avg8", "exp_avg_sq8", "exp_avg_exp", "exp_avg_sq_exp") if have == "fp8" else ("exp_avg", "exp_avg_sq")
+            keys = ("exp_avg8", "exp_avg_sq8", "exp_avg_exp", "exp_avg_sq_exp") if have == "fp8" else tuple(self._moment_keys[b] for b in self._element_moments)
             want = (total, total, total // _BLOCK, total // _BLOCK)
             if any(sd.get(k) is None or sd[k].numel() != n for k, n in zip(keys, want)):
                 raise ValueError("FusedAdamW.load_state_dict: moment buffers do not match the flat layout")
             dev = f["p"].device
             if have == self.state_precision:
-                for k, b in zip(keys, ("m8", "v8", "m_exp", "v_exp") if have == "fp8" else ("m", "v")):
+                for k, b in zip(keys, ("m8", "v8", "m_exp", "v_exp") if have == "fp8" else self._element_moments):
                     f[b].copy_(sd[k])
             elif have == "fp32":              # fp32 checkpoint -> fp8 state: the bytes the update kernel would have stored at (seed, step)
                 for k, q, e, fmt in (("exp_avg", "m8", "m_exp", "m"), ("exp_avg_sq", "v8", "v_exp", "v")):
@@ -504,6 +507,127 @@ class FusedProdigy(FusedAdamW):
             f[buf].copy_(sd[key])
 
 
+class FusedCAME(FusedAdamW):
+    """CAME, the memory-saving optimizer of the reference's factory (``train.optimizer.type: came``; its orv/utils.py:136-150), fused on the flat
+    storage of ``FusedAdamW``: same flat bf16 parameter and gradient buffers, device-side clip coefficient, usage mask, overlapped gradient
+    exchange and per-parameter skip; only the update differs.  The rule restates ``came_pytorch``'s ``CAME.step`` from
+    memory (unpinned: the package is not available to compare against; one parameter group) and is written out in
+    ``orv_amd/csrc/optim_came.hip``.  State: ONE fp32 moment per element, and for every parameter of two or more dimensions a row and a column
+    vector per matrix of its last two dimensions, twice (second moment, confidence) - about 4 bytes per element where AdamW keeps 8.  No
+    element-sized second moment is ever allocated; parameters of fewer than two dimensions keep an fp32 ``v`` of their own size.  A step is
+    seven stream-ordered launches and reads nothing on the host.  Under data parallel every rank holds the same summed gradient and therefore
+    computes the same statistics; no collective is added.
+
+    ``param_precision``: ``"bf16"`` (the reference's own arithmetic: the updated weight is rounded to bf16, nearest-even) or ``"split_fp32"``
+    (the exact fp32 master of ``FusedAdamW``).  From the reference's yaml: ``FusedCAME(params, lr=learning_rate, betas=(beta1, beta2, beta3),
+    weight_decay=weight_decay, max_grad_norm=max_grad_norm)``."""
+
+    _checkpoint_kind = "came"            # state_dict()["optimizer"]
+    _element_moments = ("m",)
+    _STATS = ("r", "c", "res_r", "res_c", "v")
+    _STAT_KEYS = {"r": "exp_avg_sq_row", "c": "exp_avg_sq_col", "res_r": "exp_avg_res_row", "res_c": "exp_avg_res_col", "v": "exp_avg_sq"}
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr, eps=(1e-30, 1e-16), clip_threshold=1.0, betas=(0.9, 0.999, 0.9999),
+                 weight_decay=0.0, max_grad_norm: float = 1.0, param_precision: str = "bf16", state_precision: str = "fp32"):
+        if param_precision not in ("bf16", "split_fp32"):
+            raise ValueError(f"FusedCAME: param_precision={param_precision!r} is not built for CAME (supported: 'bf16', 'split_fp32')")
+        if state_precision != "fp32":
+            raise ValueError(f"FusedCAME: state_precision={state_precision!r} is not built for CAME (supported: 'fp32')")
+        if not lr > 0:
+            raise ValueError(f"FusedCAME: lr={lr} must be greater than 0 (supported: lr > 0; CAME has no default learning rate)")
+        if len(betas) != 3 or not all(0.0 <= float(b) <= 1.0 for b in betas):
+            raise ValueError(f"FusedCAME: betas={tuple(betas)} (supported: three values (beta1, beta2, beta3), each in [0, 1])")
+        if len(eps) != 2 or not float(eps[0]) > 0 or float(eps[1]) < 0:
+            raise ValueError(f"FusedCAME: eps={tuple(eps)} (supported: (eps1, eps2) with eps1 > 0 - an all-zero gradient divides by it - and eps2 >= 0)")
+        if not clip_threshold > 0:
+            raise ValueError(f"FusedCAME: clip_threshold={clip_threshold} must be greater than 0 (supported: clip_threshold > 0)")
+        super().__init__(params, lr=lr, betas=tuple(float(b) for b in betas), eps=tuple(float(e) for e in eps), weight_decay=weight_decay,
+                         max_grad_norm=max_grad_norm, param_precision=param_precision, state_precision="fp32")
+        self.clip_threshold = float(clip_threshold)
+
+    def _build(self):
+        super()._build()                 # allocates m only (``_element_moments``)
+        f = self._flat
+        dev = f["p"].device
+        geo = ops.came_geometry([p.shape for p in self.params])
+        count = {"r": geo["n_rows"], "c": geo["n_cols"], "res_r": geo["n_rows"], "res_c": geo["n_cols"], "v": geo["n_v"]}
+        f.update(came_geo=geo, came_geom=torch.tensor(geo["table"], dtype=torch.int64, device=dev),
+                 came_stats={k: torch.zeros(n, dtype=torch.float32, device=dev) if n else None for k, n in count.items()},
+                 came_scratch=torch.zeros(geo["n_scratch"], dtype=torch.float32, device=dev))     # allocated once; rewritten by every step
+
+    def _launch_update(self, f, clip):
+        if "lo" in f:
+            self._drop_stale_param_lo()
+        ops.came_step(f["p"], f["g"], f["m"], f["came_stats"], f["seg_start"], f["active"], f["came_geom"], f["came_geo"], f["came_scratch"],
+                      self.param_groups[0]["lr"], self.betas, self.eps, self.clip_threshold, self.weight_decay, clip, lo=f.get("lo"),
+                      mode=ops.ADAMW_MODES[self.param_precision])
+
+    @torch.no_grad()
+    def came_state(self):
+        """Per-parameter copies of the state, shaped as ``came_pytorch`` keeps it (``self.params`` order): a list of dicts with ``exp_avg`` and
+        either ``exp_avg_sq_row`` / ``exp_avg_res_row`` ``[..., R]`` and ``exp_avg_sq_col`` / ``exp_avg_res_col`` ``[..., C]``, or, for a
+        parameter of fewer than two dimensions, ``exp_avg_sq``.  For tests and exports."""
+        if self._flat is None:
+            self._build()
+        f = self._flat
+        st, out = f["came_stats"], []
+        for p, o, row in zip(self.params, f["offs"], f["came_geo"]["table"]):
+            B, R, C, _, _, row0, col0, v0 = row[:8]
+            d = {"exp_avg": f["m"][o:o + p.numel()].view(p.shape).clone()}
+            if R:
+                lead = tuple(p.shape[:-2])
+                for k, a, n, dim in (("r", row0, B * R, R), ("c", col0, B * C, C), ("res_r", row0, B * R, R), ("res_c", col0, B * C, C)):
+                    d[self._STAT_KEYS[k]] = st[k][a:a + n].view(lead + (dim,)).clone()
+            else:
+                d["exp_avg_sq"] = st["v"][v0:v0 + p.numel()].view(p.shape).clone()
+            out.append(d)
+        return out
+
+    @torch.no_grad()
+    def last_clip(self):
+        """``(k, rms)`` of the last step: per parameter the divisor ``max(1, RMS(u) / clip_threshold)`` and the RMS of ``u`` before it
+        (fp32 tensors on the device, ``self.params`` order; meaningless for a parameter the last step skipped).  For logging and tests."""
+        if self._flat is None:
+            self._build()
+        pairs = self._flat["came_scratch"][-2 * len(self.params):].view(-1, 2)
+        return pairs[:, 0].clone(), pairs[:, 1].clone()
+
+    def state_bytes(self):
+        """Resident bytes of (optimizer state, scratch): m and the statistics; the partial sums and factors one step rewrites."""
+        if self._flat is None:
+            self._build()
+        f = self._flat
+        nbytes = lambda t: 0 if t is None else t.numel() * t.element_size()
+        return nbytes(f["m"]) + sum(nbytes(t) for t in f["came_stats"].values()), nbytes(f["came_scratch"])
+
+    # ---- checkpointing ----
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["optimizer"] = "came"
+        for k in self._STATS:
+            sd["came_" + k] = None if self._flat is None else self._flat["came_stats"][k]
+        sd["came_shapes"] = [list(p.shape) for p in self.params]
+        return sd
+
+    def load_state_dict(self, sd):
+        if sd.get("optimizer") != "came":
+            raise ValueError(f"FusedCAME.load_state_dict: the checkpoint was written by the {sd.get('optimizer') or 'adamw'!r} optimizer; CAME keeps "
+                             "a factored second moment and a confidence term that such a checkpoint does not hold (supported: checkpoints of FusedCAME)")
+        if sd.get("came_shapes") is not None and [list(s) for s in sd["came_shapes"]] != [list(p.shape) for p in self.params]:
+            raise ValueError("FusedCAME.load_state_dict: the checkpoint was written for parameters of other shapes; the factored statistics "
+                             "follow the last two dimensions and cannot be mapped")
+        super().load_state_dict(sd)
+        if sd.get("exp_avg") is None:
+            return
+        st = self._flat["came_stats"]
+        for k in self._STATS:
+            src = sd.get("came_" + k)
+            if (src is None) != (st[k] is None) or (src is not None and src.numel() != st[k].numel()):
+                raise ValueError(f"FusedCAME.load_state_dict: came_{k} does not match the flat layout")
+            if src is not None:
+                st[k].copy_(src)
+
+
 _OPTIMIZERS = ("adam (weight_decay == 0 only)", "adamw", "prodigy")
 
 
@@ -518,8 +642,8 @@ def get_optimizer(params_to_optimize, optimizer_name: str = "adam", learning_rat
     ``seed=`` for ``FusedAdamW``; ``d0=``, ``d_coef=``, ``growth_rate=`` for ``FusedProdigy`` - and any other name is refused with the
     accepted set.  ``adamw`` -> ``FusedAdamW`` (``use_8bit``: fp8
     moments), ``adam`` -> the same where Adam and AdamW coincide (``weight_decay == 0``), ``prodigy`` -> ``FusedProdigy``; an unknown name falls
-    back to ``adamw`` with a warning as the reference does.  CAME, 4-bit / torchao / DeepSpeed / CPU-offloaded optimizers are not built and
-    are refused.  ``params_to_optimize``: an iterable of parameters, or the reference's list of one ``{"params": ..., "lr": ...}`` dict (its
+    back to ``adamw`` with a warning as the reference does.  ``came`` is refused here with a pointer to ``FusedCAME``, which is constructed
+    directly; 4-bit / torchao / DeepSpeed / CPU-offloaded optimizers are not built and are refused.  ``params_to_optimize``: an iterable of parameters, or the reference's list of one ``{"params": ..., "lr": ...}`` dict (its
     ``lr`` wins over ``learning_rate``, as in torch)."""
     import warnings
     supported = f"supported: optimizer_name in {', '.join(_OPTIMIZERS)}; use_8bit with adam / adamw (fp8 moments)"
@@ -532,7 +656,8 @@ def get_optimizer(params_to_optimize, optimizer_name: str = "adam", learning_rat
         warnings.warn(f"get_optimizer: optimizer_name={name!r} is not known ({supported}); falling back to 'adamw'")
         name = "adamw"
     if name == "came":
-        raise ValueError(f"get_optimizer: CAME is not built here ({supported})")
+        raise ValueError("get_optimizer: CAME is not built into get_optimizer yet: construct orv_amd.FusedCAME(params, lr=learning_rate, "
+                         f"betas=(beta1, beta2, beta3), weight_decay=weight_decay, max_grad_norm=max_grad_norm) directly ({supported})")
     if use_8bit and name not in ("adam", "adamw"):
         raise ValueError(f"get_optimizer: use_8bit=True goes with adam / adamw only, not with {name!r} ({supported})")
     params = list(params_to_optimize)
