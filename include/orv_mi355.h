@@ -815,6 +815,30 @@ int orv_frames_quantize(const void* src, int src_bytes, long src_extent, const l
 int orv_frames_handoff(const unsigned char* src, long src_extent, const long* src_stride, int B, int F, int H, int W, int frame,
                        const void* table, void* out, void* stream);
 
+/* -- First-block step cache of the denoise loop (opt-in, lossy) ----------------------------------------------------------------------------
+ * The contract is DESIGN.md section 20; the rule is restated from memory of diffusers' FirstBlockCache / ParaAttention's FBCache and is
+ * not pinned against either.  x is the joint bf16 buffer [B, S = Nt + Nv, D] with row stride D; only the video rows Nt .. S - 1 of every
+ * clip take part.  e, p, f, c, t are dense bf16 [B, Nv, D].  D is a multiple of 64, every tensor pointer 16-byte aligned.  Symbols: E the
+ * video rows after the embedding stage, F after iteration 0 of the block loop, X after the last iteration, p the stored first residual, t
+ * the stored tail residual.  Every argument is checked before any launch and no device pointer is followed on the host.  Streaming
+ * kernels, 16-byte accesses, plain vector stores, no atomics: two runs give the same bits.
+ *
+ * Doubles of caller scratch orv_step_cache_probe needs for (B, Nv, D): two per workgroup; -1 with orv_last_error() for a bad shape. */
+long orv_step_cache_scratch(int B, int Nv, int D);
+/* x holds F in its video rows, e holds E.  Writes f = F (a dense copy, the same bits), c = bf16_rne(fp32(F) - fp32(E)) (one fp32
+ * subtraction, one rounding) and sums fp64 [B, 2]: sums[b][0] = num_b = sum |fp32(c) - fp32(p)| and sums[b][1] = den_b = sum |fp32(p)|
+ * over the clip's Nv D values; each difference is rounded once to fp32, its absolute value widened to fp64 and added in fp64, in an
+ * order fixed by (Nv, D).  A NaN among the values read makes the sum it enters NaN.  scratch (n_scratch doubles, at least
+ * orv_step_cache_scratch) needs no initial value: every word read is written first.  Two launches (partial sums per workgroup, then
+ * one wave per clip).  Traffic: 5 B Nv D 2 bytes. */
+int orv_step_cache_probe(const void* x, const void* e, const void* p, void* f, void* c, double* scratch, long n_scratch, double* sums, int B,
+                         int Nt, int Nv, int D, void* stream);
+/* x holds X in its video rows.  Writes t = bf16_rne(fp32(X) - fp32(f)) and p = c (the commit of the probe's residual, fused in: no
+ * separate copy, no pointer swap).  Traffic: 5 B Nv D 2 bytes. */
+int orv_step_cache_store(const void* x, const void* f, const void* c, void* t, void* p, int B, int Nt, int Nv, int D, void* stream);
+/* The video rows of x become bf16_rne(fp32(x) + fp32(t)), in place; the text rows are not touched.  Traffic: 3 B Nv D 2 bytes. */
+int orv_step_cache_apply(void* x, const void* t, int B, int Nt, int Nv, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,10 @@ SIGNATURES = {
     "orv_lm_compose": (c_int, [c_void_p] + [c_int] * 5 + [c_long, c_long, c_float, c_void_p, c_int] + [c_void_p] * 6),
     "orv_frames_quantize": (c_int, [c_void_p, c_int, c_long, c_void_p] + [c_int] * 5 + [c_void_p, c_long, c_long, c_long, c_int, c_void_p]),
     "orv_frames_handoff": (c_int, [c_void_p, c_long, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p]),
+    "orv_step_cache_scratch": (c_long, [c_int, c_int, c_int]),
+    "orv_step_cache_probe": (c_int, [c_void_p] * 6 + [c_long, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "orv_step_cache_store": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "orv_step_cache_apply": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
 }
 
 _lib = None

@@ -393,6 +393,8 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
         self._ws: Dict[Any, Dict[str, torch.Tensor]] = {}
         self._mxfp8 = False         # MXFP8 inference mode of the block GEMMs (enable_mxfp8)
         self._mx_gen = 0            # bumped by every enable_mxfp8 call: part of GraphedTransformer's key
+        self._step_cache = None     # first-block step cache (enable_step_cache); None: off
+        self._sc_gen = 0            # bumped by every enable_step_cache call: part of GraphedTransformer's key
         self._mx_cache = None       # per block: (weight key, quantised QKV / out / FFN1 / FFN2 weights)
         self._lora_init()           # LoRA adapters of the attention projections (orv_amd/lora.py)
         self._set_zeros()
@@ -746,6 +748,12 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
         if self._mxfp8 and (self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
             raise RuntimeError("MXFP8 mode is inference-only: call model.eval() and run under torch.no_grad() (or "
                                "requires_grad_(False)), or turn it off with enable_mxfp8(False) before training")
+        if self._step_cache is not None:
+            from .step_cache import SUPPORTED as _SC_SUPPORTED
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                raise RuntimeError(f"step cache: this forward records gradients; {_SC_SUPPORTED} - or disable_step_cache()")
+            if _chains() > 1:
+                raise RuntimeError(f"step cache: ORV_CHAINS = {_chains()}; {_SC_SUPPORTED} (the segments stay single-stream)")
         if not hidden_states.is_cuda:
             raise RuntimeError("orv_amd runs on MI355X only: move the model and its inputs to the GPU (no CPU fallback)")
         # attention_kwargs["scale"] multiplies the active adapter's coefficient for this call (:729-741); ignored without an adapter
@@ -874,26 +882,43 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
 
     def _forward_inference(self, hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs,
                            image_rotary_emb, return_dict, num_views=1, image_rotary_emb_view=None, lora=None):
-        """Workspace lookup -> ``stages.embed`` -> score-bound priming -> blocks -> ``stages.head``."""
+        """Workspace lookup -> ``stages.embed`` -> score-bound priming -> blocks -> ``stages.head``.  With the
+        step cache on (section 20) the block loop is cut behind iteration 0 and behind the last iteration: ``StepCache.run``."""
+        ctx = self._inference_front(hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs, image_rotary_emb,
+                                    return_dict, num_views, image_rotary_emb_view, lora)
+        if self._step_cache is not None:
+            return self._step_cache.run(self, ctx)
+        self._run_blocks(ctx, 0, len(self.transformer_blocks))
+        return self._inference_head(ctx)
+
+    def _inference_front(self, hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs, image_rotary_emb, return_dict,
+                         num_views, image_rotary_emb_view, lora):
+        """Everything ahead of the block loop -> the forward's context: shapes, workspace, the embed stage's outputs, block operands."""
         c = self.config
         sh = stages.shapes(hidden_states, encoder_hidden_states, num_views, c)
-        B, S, Nt, D, M, T = sh.B, sh.S, sh.Nt, sh.D, sh.M, sh.T
-        ws = self._workspace(B, S, sh.Nv, hidden_states.device)
-        x, xn, hbuf, packed = ws["x"], ws["xn"], ws["h"], ws["packed"]
-        st = stages.embed(self, sh, x, hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs, image_rotary_emb,
+        ws = self._workspace(sh.B, sh.S, sh.Nv, hidden_states.device)
+        st = stages.embed(self, sh, ws["x"], hidden_states, encoder_hidden_states, controls_or_guidances, timestep, ofs, image_rotary_emb,
                           image_rotary_emb_view)
-        mod, grp, rope, mv = st.mod, st.grp, st.rope, st.mv
-
-        # transformer blocks (:861-907 -> :394-445)
-        mb, mg = sh.G * 3 * D, 3 * D
         scale = 1.0 / math.sqrt(c.attention_head_dim)
-        prime_score_bounds([b.attn1 for b in self.transformer_blocks], scale, rope=rope is not None)
-        if mv is not None:
+        prime_score_bounds([b.attn1 for b in self.transformer_blocks], scale, rope=st.rope is not None)
+        if st.mv is not None:
             prime_score_bounds([b.attn1 for b in self.mv_blocks], scale, rope=st.rope_view is not None)
-        mxw = self._mxfp8_weights() if self._mxfp8 else None
-        for i, blk in enumerate(self.transformer_blocks):
+        from types import SimpleNamespace
+        return SimpleNamespace(sh=sh, ws=ws, st=st, x=ws["x"], scale=scale, lora=lora, num_views=num_views, return_dict=return_dict,
+                               mxw=self._mxfp8_weights() if self._mxfp8 else None)
+
+    def _run_blocks(self, ctx, i0, i1):
+        """Iterations [i0, i1) of the block loop (:861-907 -> :394-445) on the joint buffer of ``ctx``."""
+        c = self.config
+        sh, ws, st, lora, mxw, scale = ctx.sh, ctx.ws, ctx.st, ctx.lora, ctx.mxw, ctx.scale
+        B, S, Nt, D, M, T = sh.B, sh.S, sh.Nt, sh.D, sh.M, sh.T
+        x, xn, hbuf, packed = ws["x"], ws["xn"], ws["h"], ws["packed"]
+        mod, grp, rope, mv = st.mod, st.grp, st.rope, st.mv
+        mb, mg = sh.G * 3 * D, 3 * D
+        for i in range(i0, i1):
+            blk = self.transformer_blocks[i]
             if mv is not None:
-                self._mv_block(self.mv_blocks[i], mv.ws, mv.mod[i], x, xn, mv.grp0, B, S, Nt, num_views, T, st.rope_view)
+                self._mv_block(self.mv_blocks[i], mv.ws, mv.mod[i], x, xn, mv.grp0, B, S, Nt, ctx.num_views, T, st.rope_view)
             m1, m2 = mod[2 * i], mod[2 * i + 1]
             if mxw is not None:
                 self._mx_block(blk, mxw[i], ws, m1, m2, mb, mg, grp, B, S, Nt, rope, scale)
@@ -910,10 +935,28 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
             ops.gemm(hbuf, f2.weight, f2.bias, x, M, D, f0.weight.shape[0], epilogue=2, R=x, ldr=D,
                      gate=m2[..., 2 * D:], gate_b=mb, gate_g=mg, grp=grp, a_packed=packed["ffn"])
 
-        output, _ = stages.head(self, sh, x, ws["vis"], ws["vis2"], st.modf)
-        if not return_dict:
+    def _inference_head(self, ctx):
+        st = ctx.st
+        output, _ = stages.head(self, ctx.sh, ctx.x, ctx.ws["vis"], ctx.ws["vis2"], st.modf)
+        if not ctx.return_dict:
             return (output, st.is_action_mask, st.actions_recon)
         return Transformer3DModelTrajOutput(sample=output, is_action_mask=st.is_action_mask, actions_recon=st.actions_recon)
+
+    # ---- first-block step cache (orv_amd/step_cache.py) ----
+    def enable_step_cache(self, threshold, max_consecutive_skips=None):
+        """Turn the opt-in, lossy first-block step cache on -> its ``StepCache``.  Every inference forward then runs the embedding and
+        the first block, and skips the remaining blocks when the first block's residual moved by less than ``threshold`` (relative L1,
+        largest over the clips) since the last computed forward; ``max_consecutive_skips`` caps runs of skipped forwards."""
+        from . import step_cache as _sc
+        if len(self.transformer_blocks) < 2:
+            raise ValueError(f"step cache: num_layers = {len(self.transformer_blocks)}; {_sc.SUPPORTED}")
+        self._sc_gen += 1
+        self._step_cache = _sc.StepCache(threshold, max_consecutive_skips, generation=self._sc_gen)
+        return self._step_cache
+
+    def disable_step_cache(self):
+        self._step_cache = None
+        return self
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1133,18 +1176,58 @@ class GraphedTransformer:
             kw["attention_kwargs"] = akw
         # MXFP8 state: a graph captured in one mode never replays in the other, nor after a re-enable (new quantised weights)
         mx = (self.tr._mx_gen,) if getattr(self.tr, "_mxfp8", False) else None
-        key = (desc, _state.weights_epoch[0], self._weights_version(), self.tr.training, _chains(), mx, lkey)
+        base = (desc, _state.weights_epoch[0], self._weights_version(), self.tr.training, _chains(), mx, lkey)
+        sc = getattr(self.tr, "_step_cache", None)
+        if sc is None:
+            return self._replay(base, kw, leaves, self._forward, self.max_entries)
+        return self._call_segments(base, kw, leaves, sc)
+
+    def _call_segments(self, base, kw, leaves, sc):
+        """A forward with the step cache on: three entries per call shape - front (embed, iteration 0, probe),
+        tail (iterations 1 .. L-1, store, head) and skip (apply, head) - with the one host read of the step between front and the rest.
+        The front entry keeps the forward's context (modulation tables, row maps, RoPE tables, workspace) alive for the other two, which
+        are captured only against a CAPTURED front: its tensors have fixed addresses then."""
+        limit = 3 * self.max_entries
+        gen = sc.generation
+
+        def front(kw_, st, concurrent):
+            sc._segment = "front"
+            try:
+                self._forward(kw_, st, concurrent)
+            finally:
+                sc._segment = None
+            st["ctx"] = sc._ctx
+            return None
+        self._replay(base + (gen, "front"), kw, leaves, front, limit)
+        fst = self._state[base + (gen, "front")]
+        sc.adopt(fst["ctx"])
+        skip = sc.decide_now()
+        run = lambda kw_, st, concurrent: sc.segment(self.tr, skip)
+        if "graph" not in fst:
+            with torch.no_grad():
+                return run(None, None, False)
+        key = base + (gen, "skip" if skip else "tail")
+        if key in self._state and self._state[key].get("front") is not fst:     # captured against a front entry that is gone
+            del self._state[key]
+        out = self._replay(key, {}, [], run, limit)
+        self._state[key]["front"] = fst
+        if base + (gen, "front") in self._state:
+            self._state.move_to_end(base + (gen, "front"))                       # never dropped ahead of its tail / skip entries
+        return out
+
+    def _replay(self, key, kw, leaves, forward, limit):
+        """``forward(kw, st, concurrent)`` under the entry ``key``: eager on the first call, captured on the second, replayed from then on."""
         st = self._state.get(key)
         if st is None:                       # eager warm-up call
             st = self._state[key] = {"calls": 1}
-            while len(self._state) > self.max_entries:
+            while len(self._state) > limit:
                 self._state.popitem(last=False)
             with torch.no_grad():
-                return self._forward(kw, st, concurrent=False)
+                return forward(kw, st, False)
         self._state.move_to_end(key)
         if st.get("eager_only"):             # a capture of this key failed before: plain launches from now on
             with torch.no_grad():
-                return self._forward(kw, st, concurrent=False)
+                return forward(kw, st, False)
         if "graph" not in st:
             st["static"] = [t.clone() for t in leaves]
             skw = self._rebuild(kw, st["static"])
@@ -1154,7 +1237,7 @@ class GraphedTransformer:
                 # thread_local: another thread's CUDA calls (a DataLoader pin_memory thread during in-training validation,
                 # base_train.yaml pin_memory / 8 workers) must not invalidate this capture
                 with torch.no_grad(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    st["out"] = self._forward(skw, st, concurrent=True)  # st["ws"]: the captured launches point into these workspaces -
+                    st["out"] = forward(skw, st, True)                   # st["ws"]: the captured launches point into these workspaces -
             except _NotCapturable:
                 raise
             except Exception as e:           # out of memory in the private pool, a syncing op, a foreign capture-unsafe call
@@ -1167,7 +1250,7 @@ class GraphedTransformer:
                               "skip the attempt)", RuntimeWarning)
                 torch.cuda.synchronize()
                 with torch.no_grad():
-                    return self._forward(kw, st, concurrent=False)
+                    return forward(kw, st, False)
             st["graph"] = g                                              # kept alive even if the model later swaps in another one
             st["lora"] = getattr(self.tr, "_lora_cached_operands", lambda: None)()   # the adapter operand copies the captured launches read
         else:
@@ -1221,6 +1304,8 @@ class CogVideoXImageToVideoPipelineTraj:
         self._guidance_scale, self._interrupt, self._num_timesteps = 1.0, False, 0
         self._graphed: Optional[GraphedTransformer] = None
         self._graph_mode: Optional[bool] = None      # None: automatic (see transformer_forward); True / False: enable_hip_graph()
+        self._step_cache_policy = (1, 1)             # (compute_first, compute_last) of enable_step_cache()
+        self._step_cache_report: List[tuple] = []
         from .components import VideoProcessor
         self.video_processor = VideoProcessor(vae_latent_channels=getattr(vcfg, "latent_channels", 16) if vcfg is not None else 16,
                                               vae_scale_factor=self.vae_scale_factor_spatial)          # :1110-1113
@@ -1467,6 +1552,28 @@ class CogVideoXImageToVideoPipelineTraj:
         self._graphed = GraphedTransformer(self.transformer) if enabled else None
         return self
 
+    def enable_step_cache(self, threshold, *, max_consecutive_skips=None, compute_first: int = 1, compute_last: int = 1):
+        """Turn the opt-in, lossy first-block step cache of the transformer on for this pipeline's denoise loops (DESIGN.md section 20;
+        ``CogVideoXTransformer3DModelTraj.enable_step_cache``) -> its ``StepCache``.  Every call (and every chunk of a ``rollout``) starts
+        cold; its first ``compute_first`` (>= 1) and last ``compute_last`` (>= 0) steps are computed whatever their distance."""
+        for name, v, lo in (("compute_first", compute_first, 1), ("compute_last", compute_last, 0)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError(f"step cache: {name} = {v!r}; supported: an integer >= {lo}")
+        sc = self.transformer.enable_step_cache(threshold, max_consecutive_skips)
+        self._step_cache_policy = (compute_first, compute_last)
+        self._step_cache_report = []
+        return sc
+
+    def disable_step_cache(self):
+        self.transformer.disable_step_cache()
+        self._step_cache_report = []
+        return self
+
+    @property
+    def step_cache_report(self):
+        """(timestep, max distance, skipped, reason) per step of the last call with the step cache on; empty with the cache off."""
+        return list(self._step_cache_report)
+
     def transformer_forward(self, **kw):
         """One transformer forward of the denoise loop (the call at cogvideox_control.py:1415-1425), the way ``__call__`` makes it.
         Default = HIP-graph replay (bit-identical to the eager launches - tests/test_gpu_model.py - and ~1 ms per B = 4 step / ~2.5 ms per
@@ -1684,9 +1791,16 @@ class CogVideoXImageToVideoPipelineTraj:
         ofs_emb = None if tr.config.ofs_embed_dim is None else latents.new_full((1,), fill_value=2.0)
         is_dpm = isinstance(sched, CogVideoXDPMScheduler)
         old_x0 = None
+        sc = getattr(tr, "_step_cache", None)
+        if sc is not None:                   # every call - every chunk of a rollout - starts cold
+            sc.reset()
+            self._step_cache_report = []
+            first, last = self._step_cache_policy
         for i, t in enumerate(ts_host):
             if self._interrupt:
                 continue
+            if sc is not None and (i < first or i >= len(ts_host) - last):
+                sc.force_compute()
             # channel-concat [latents | image_latents] (:1409-1413)
             x_in = torch.cat([latents] * 2) if do_cfg else latents
             img_in = torch.cat([image_latents] * 2) if do_cfg else image_latents
@@ -1695,6 +1809,9 @@ class CogVideoXImageToVideoPipelineTraj:
             noise_pred = self.transformer_forward(hidden_states=model_in, encoder_hidden_states=prompt_embeds, timestep=tvec, ofs=ofs_emb,
                              image_rotary_emb=image_rotary_emb, attention_kwargs=attention_kwargs,
                              controls_or_guidances=controls, return_dict=False, num_views=num_views)[0]
+            if sc is not None:
+                rec = sc.history[-1]
+                self._step_cache_report.append((t, rec.max_distance, rec.skipped, rec.reason))
             gs = guidance_scale
             if use_dynamic_cfg:
                 gs = 1 + guidance_scale * ((1 - math.cos(math.pi * ((num_inference_steps - t) / num_inference_steps) ** 5.0)) / 2)

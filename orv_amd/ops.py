@@ -1403,3 +1403,62 @@ def frames_handoff(frames, index: int, table):
         check(lib().orv_frames_handoff(_p(frames), _behind(frames), (ctypes.c_long * 5)(*frames.stride()), B, F, H, W, index, _p(table), _p(out),
                                        _stream()), "orv_frames_handoff")
     return out
+
+
+# ---- first-block step cache (csrc/step_cache.hip) ----
+def _sc_dense(named, B, Nv, D):
+    for t, n in named:
+        _need_c(t, BF16, n)
+        if t.numel() != B * Nv * D:
+            raise ValueError(f"orv_amd.ops: `{n}` must hold [B = {B}, Nv = {Nv}, D = {D}] values (got {tuple(t.shape)})")
+
+
+def _sc_joint(x, B, Nt, Nv, D):
+    _need_c(x, BF16, "x")
+    if min(B, Nv, D) < 1 or Nt < 0 or x.numel() != B * (Nt + Nv) * D:
+        raise ValueError(f"orv_amd.ops: `x` must be the joint buffer [B = {B}, Nt + Nv = {Nt} + {Nv}, D = {D}] (got {tuple(x.shape)})")
+
+
+def step_cache_scratch(B: int, Nv: int, D: int) -> int:
+    """Doubles of scratch ``step_cache_probe`` needs for this shape."""
+    n = lib().orv_step_cache_scratch(B, Nv, D)
+    if n < 0:
+        check(1, "orv_step_cache_scratch")
+    return int(n)
+
+
+def step_cache_probe(x, e, p, f, c, sums, B, Nt, Nv, D, scratch=None):
+    """x: the joint bf16 buffer [B, Nt + Nv, D] after iteration 0; e, p: dense bf16 [B, Nv, D] (embedding output, stored first residual).
+    Writes f (dense copy of x's video rows), c = bf16(f - e) and ``sums`` fp64 [B, 2] = (sum |c - p|, sum |p|) per clip; -> sums."""
+    _sc_joint(x, B, Nt, Nv, D)
+    _sc_dense(((e, "e"), (p, "p"), (f, "f"), (c, "c")), B, Nv, D)
+    _need_c(sums, torch.float64, "sums")
+    if sums.numel() != 2 * B:
+        raise ValueError(f"orv_amd.ops: `sums` must be fp64 [B = {B}, 2] (got {tuple(sums.shape)})")
+    if scratch is None:
+        scratch = torch.empty(step_cache_scratch(B, Nv, D), dtype=torch.float64, device=x.device)
+    _need_c(scratch, torch.float64, "scratch")
+    _same_device((x, "x"), (e, "e"), (p, "p"), (f, "f"), (c, "c"), (sums, "sums"), (scratch, "scratch"))
+    with _timed(("step_cache_probe", B, Nv, D)):
+        check(lib().orv_step_cache_probe(_p(x), _p(e), _p(p), _p(f), _p(c), _p(scratch), scratch.numel(), _p(sums), B, Nt, Nv, D, _stream()),
+              "orv_step_cache_probe")
+    return sums
+
+
+def step_cache_store(x, f, c, t, p, B, Nt, Nv, D):
+    """x: the joint buffer after the last iteration.  Writes t = bf16(x's video rows - f) and p = c."""
+    _sc_joint(x, B, Nt, Nv, D)
+    _sc_dense(((f, "f"), (c, "c"), (t, "t"), (p, "p")), B, Nv, D)
+    _same_device((x, "x"), (f, "f"), (c, "c"), (t, "t"), (p, "p"))
+    with _timed(("step_cache_store", B, Nv, D)):
+        check(lib().orv_step_cache_store(_p(x), _p(f), _p(c), _p(t), _p(p), B, Nt, Nv, D, _stream()), "orv_step_cache_store")
+
+
+def step_cache_apply(x, t, B, Nt, Nv, D):
+    """The video rows of the joint buffer x become bf16(x + t), in place; -> x."""
+    _sc_joint(x, B, Nt, Nv, D)
+    _sc_dense(((t, "t"),), B, Nv, D)
+    _same_device((x, "x"), (t, "t"))
+    with _timed(("step_cache_apply", B, Nv, D)):
+        check(lib().orv_step_cache_apply(_p(x), _p(t), B, Nt, Nv, D, _stream()), "orv_step_cache_apply")
+    return x
