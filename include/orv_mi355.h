@@ -370,6 +370,18 @@ typedef struct {
 } orv_came_t;
 int orv_came_launch(const orv_came_t* d, int which, void* stream);
 int orv_came_step(const orv_came_t* d, void* stream);
+/* Exponential moving average of the weights on the flat layout of orv_adamw_flat_ex (orv_amd.FusedEMA; defined bit for
+ * bit in orv_amd/csrc/optim_ema.hip).  shadow fp32[n] lies in the segment layout of p bf16[n]; lo int16[n] (NULL where the optimizer
+ * keeps none) holds the low halves of the fp32 masters.
+ *   orv_ema_update  - shadow <- shadow - one_minus_decay * (shadow - theta), three separately rounded fp32 operations in that order;
+ *                     theta is the master (p_bits << 16) + sign_extend(lo) where lo is given, fp32(p) otherwise.  Padding stays +0.
+ *   orv_ema_swap_in - stash_p <- p and stash_lo <- lo (each may be NULL: not kept), then p <- the nearest-even bf16 of shadow (NaN quiet);
+ *                     zero_lo != 0 also clears lo, so that the master equals the written value.  One launch.
+ * Workgroups of 2048 elements, 16-byte accesses, no atomics.  A null required buffer, n % 2048 != 0, a buffer that is not 16-byte
+ * aligned, one_minus_decay outside [0, 1], or stash_lo / zero_lo without lo return non-zero with an orv_last_error message before
+ * anything is launched. */
+int orv_ema_update(float* shadow, const void* p, const void* lo, long n, float one_minus_decay, void* stream);
+int orv_ema_swap_in(void* p, void* lo, const float* shadow, void* stash_p, void* stash_lo, long n, int zero_lo, void* stream);
 /* dst_ptr[s][j] = bf16(src[src_off[s] + j]), j < len[s], for nseg segments (src_off / dst_ptr / len are DEVICE arrays; dst_ptr holds
  * device addresses of bf16 storage; max_len = max len[s]): the small fp32-accumulated parameter gradients go from the backward's
  * accumulator arena into the fused optimizer's flat gradient buffer in one launch (the reference leaves this to autograd's

@@ -26,6 +26,10 @@ def __getattr__(name):
     if name in ("FusedProdigy", "FusedCAME", "get_optimizer"):
         from . import optim
         return getattr(optim, name)
+    # the weight average to sample from (orv_amd/ema.py), resolved on first use likewise
+    if name == "FusedEMA":
+        from .ema import FusedEMA
+        return FusedEMA
     # the scoring stage of the reference's workflow (orv_amd/metrics.py), resolved on first use likewise
     if name in ("frame_metrics", "psnr_ssim", "frechet_distance"):
         from . import metrics

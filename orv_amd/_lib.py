@@ -134,6 +134,8 @@ SIGNATURES = {
                                    c_int, c_void_p]),
     "orv_came_launch": (c_int, [POINTER(Came), c_int, c_void_p]),
     "orv_came_step": (c_int, [POINTER(Came), c_void_p]),
+    "orv_ema_update": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p]),
+    "orv_ema_swap_in": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]),
     "orv_scatter_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "orv_sumsq": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "orv_head_transpose": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -685,6 +685,46 @@ def came_step(p, g, m, stats, seg_start, seg_active, geom, sizes, scratch, lr, b
         check(lib().orv_came_launch(d, which, _stream()), "orv_came_launch")
 
 
+def _need_ema_layout(what, named):
+    """Every buffer of an EMA launch: on the GPU, of its dtype, contiguous, 16-byte aligned, all of one length that is a multiple of 2048."""
+    n = named[0][1].numel()
+    for name, t, dtype in named:
+        if t is None:
+            continue
+        _need(t, dtype, name)
+        if not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+        if t.numel() != n:
+            raise RuntimeError(f"orv_amd.ops: {what}: `{name}` holds {t.numel()} elements, `{named[0][0]}` {n} (one flat layout)")
+        if t.data_ptr() % 16:
+            raise RuntimeError(f"orv_amd.ops: {what}: `{name}` must be 16-byte aligned (the kernel moves 16 bytes per access)")
+    if n == 0 or n % 2048:
+        raise RuntimeError(f"orv_amd.ops: {what}: {n} elements; the flat layout is a positive multiple of 2048 (pad every segment)")
+    return n
+
+
+def ema_update(shadow, p, lo=None, one_minus_decay=0.0):
+    """``shadow <- shadow - one_minus_decay * (shadow - theta)`` over a whole flat buffer in one launch (``orv_ema_update``): ``shadow``
+    fp32 in the layout of ``p`` (bf16), ``theta`` the fp32 master ``p | lo`` where ``lo`` (int16) is given, else ``fp32(p)``."""
+    n = _need_ema_layout("ema_update", (("shadow", shadow, torch.float32), ("p", p, BF16), ("lo", lo, torch.int16)))
+    omd = float(one_minus_decay)
+    if not 0.0 <= omd <= 1.0:
+        raise RuntimeError(f"orv_amd.ops: ema_update: one_minus_decay={one_minus_decay} must lie in [0, 1]")
+    check(lib().orv_ema_update(_p(shadow), _p(p), _p(lo), n, omd, _stream()), "orv_ema_update")
+
+
+def ema_swap_in(p, shadow, lo=None, stash_p=None, stash_lo=None, zero_lo=False):
+    """``stash_p <- p``, ``stash_lo <- lo`` (where given), then ``p <- bf16_rne(shadow)`` and, with ``zero_lo``, ``lo <- 0`` - one launch
+    (``orv_ema_swap_in``)."""
+    n = _need_ema_layout("ema_swap_in", (("p", p, BF16), ("shadow", shadow, torch.float32), ("lo", lo, torch.int16),
+                                         ("stash_p", stash_p, BF16), ("stash_lo", stash_lo, torch.int16)))
+    if lo is None and (stash_lo is not None or zero_lo):
+        raise RuntimeError("orv_amd.ops: ema_swap_in: `stash_lo` / `zero_lo` given without the low-half buffer `lo`")
+    if stash_lo is not None and stash_p is None:
+        raise RuntimeError("orv_amd.ops: ema_swap_in: `stash_lo` given without `stash_p`")
+    check(lib().orv_ema_swap_in(_p(p), _p(lo), _p(shadow), _p(stash_p), _p(stash_lo), n, int(bool(zero_lo)), _stream()), "orv_ema_swap_in")
+
+
 STATE8_FORMATS = {"m": 0, "v": 1}         # first moment: e4m3fn, second moment: e5m2 (orv_amd/csrc/optim_s8.hip)
 
 

@@ -140,7 +140,7 @@ def sft_loss(transformer, scheduler, b: Batch, noise: torch.Tensor, timesteps: t
 
 def sft_step(transformer, scheduler, optimizer, b: Batch, generator: Optional[torch.Generator] = None,
              use_rope: bool = False, is_ofs_embed: bool = False, data_parallel: bool = False,
-             gradient_accumulation_steps: int = 1, micro_step: int = 0, lr_scheduler=None):
+             gradient_accumulation_steps: int = 1, micro_step: int = 0, lr_scheduler=None, ema=None):
     """One micro-batch of the loop body (:863-1107).  ``optimizer`` is ``orv_amd.optim.FusedAdamW`` (global-norm clip inside,
     on device).  With ``data_parallel`` the flat bf16 gradient buffer is averaged over the RCCL group.
 
@@ -156,7 +156,8 @@ def sft_step(transformer, scheduler, optimizer, b: Batch, generator: Optional[to
     in every shipped config) is stepped once per call, behind the optimizer, as ``lr_scheduler.step()`` at :1107 is - accelerate's wrapper
     then skips it on non-synchronising micro-batches and steps it ``num_processes`` times on synchronising ones, which is why the script
     multiplies the warm-up / total counts by ``num_processes``: here it advances by ``world`` on synchronising micro-batches.  Returns
-    ``(loss, parts)``; ``parts["grad_norm"]`` is present on synchronising micro-batches only."""
+    ``(loss, parts)``; ``parts["grad_norm"]`` is present on synchronising micro-batches only.  ``ema`` (``orv_amd.FusedEMA`` over this
+    optimizer) is stepped on synchronising micro-batches, behind the optimizer: one more launch; with ``None`` nothing is added."""
     dev = b.video_latents.device
     noise = torch.randn(b.video_latents.shape, device=dev, dtype=torch.float32, generator=generator).to(b.video_latents.dtype)
     timesteps = torch.randint(0, scheduler.config.num_train_timesteps, (b.video_latents.shape[0],), dtype=torch.int64,
@@ -177,6 +178,8 @@ def sft_step(transformer, scheduler, optimizer, b: Batch, generator: Optional[to
     if sync:
         parts["grad_norm"] = optimizer.step(average_over=world)       # (finishes) the exchange, averages, clips, updates
         optimizer.zero_grad()
+        if ema is not None:
+            ema.step()
         if lr_scheduler is not None:                                  # :1107 through accelerate's AcceleratedScheduler (split_batches False)
             for _ in range(world):
                 lr_scheduler.step()
