@@ -851,6 +851,37 @@ int orv_step_cache_store(const void* x, const void* f, const void* c, void* t, v
 /* The video rows of x become bf16_rne(fp32(x) + fp32(t)), in place; the text rows are not touched.  Traffic: 3 B Nv D 2 bytes. */
 int orv_step_cache_apply(void* x, const void* t, int B, int Nt, int Nv, int D, void* stream);
 
+/* -- Training-state snapshot with a checksum per tensor (orv_amd.train_state) ------------------------------------------
+ * The checksum of a buffer of `bytes` bytes, all arithmetic mod 2^64: pad the bytes with zero bytes to a multiple of 4, read them as
+ * little-endian u32 words w_0 .. w_{W-1}; s1 = sum w_i, s2 = sum (i + 1) w_i; an empty buffer gives (0, 0).  Bytes 01 00 00 00 02 00 00 00 03
+ * are the words 1, 2, 3: s1 = 6, s2 = 14.
+ *
+ * One table entry: `bytes` bytes at src, copied to dst (NULL: summed only).  src and dst are 4-byte aligned, independently at any
+ * residue mod 16; bytes is any count >= 0; the two ranges of an entry do not overlap.  Nothing is written outside [dst, dst + bytes). */
+typedef struct {
+    const void* src;
+    void* dst;
+    long bytes;
+} orv_snapshot_entry_t;
+/* The chunk size of the kernels: an entry is processed in pieces of this many bytes of its own range. */
+int orv_snapshot_chunk_bytes(void);
+/* Bytes of caller scratch that suffice for any table of n entries holding total_bytes bytes in all (16 per chunk, at most one partly
+ * filled chunk per entry); -1 with orv_last_error() for a bad argument. */
+long orv_snapshot_scratch_bytes(int n, long total_bytes);
+/* Copies every entry and writes sums u64 [n][2] = (s1, s2) per entry.  `entries` is the DEVICE table the kernels read; `entries_host` holds
+ * the same n entries in host memory: every pointer and count is checked there before any launch, no device pointer is followed on the
+ * host, and a table the two copies disagree on is the caller's error (the kernels stay inside the table and the scratch either way).
+ * Refused with ORV_EINVAL and a message, without a launch: a null table, n outside 1 .. 2^20, a null or unaligned sums, a null src with
+ * bytes > 0, a src or dst that is not 4-byte aligned, overlapping ranges, a scratch that is null, not 16-byte aligned or smaller than
+ * 16 bytes per chunk of this table.  Two launches for the whole table, whatever n is: one pass over the data (16-byte accesses, plain
+ * vector stores, one pair of partial sums per chunk into scratch) and one combine pass (one workgroup per entry); no atomics, so two
+ * runs give the same bits, and scratch needs no initial value.  Traffic: 2 x bytes for a copied entry, 1 x for a summed one. */
+int orv_snapshot(const orv_snapshot_entry_t* entries, const orv_snapshot_entry_t* entries_host, int n, unsigned long long* sums,
+                 void* scratch, long scratch_bytes, void* stream);
+/* The same sums with no copy: every dst of the table must be NULL (refused otherwise), nothing but sums and scratch is written. */
+int orv_checksum(const orv_snapshot_entry_t* entries, const orv_snapshot_entry_t* entries_host, int n, unsigned long long* sums,
+                 void* scratch, long scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

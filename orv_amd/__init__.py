@@ -30,6 +30,10 @@ def __getattr__(name):
     if name == "FusedEMA":
         from .ema import FusedEMA
         return FusedEMA
+    # resumable training-state checkpoints (orv_amd/train_state.py), resolved on first use likewise
+    if name in ("save_state", "load_state", "latest_checkpoint", "SaveHandle"):
+        from . import train_state
+        return getattr(train_state, name)
     # the scoring stage of the reference's workflow (orv_amd/metrics.py), resolved on first use likewise
     if name in ("frame_metrics", "psnr_ssim", "frechet_distance"):
         from . import metrics

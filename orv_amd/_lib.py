@@ -39,6 +39,10 @@ class Frames(Structure):
     _fields_ = [("data", c_void_p), ("kind", c_int), ("h", c_int), ("w", c_int), ("extent", c_long), ("offset", c_long), ("stride", c_long * 4)]
 
 
+class SnapshotEntry(Structure):      # orv_snapshot_entry_t
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("bytes", c_long)]
+
+
 class Came(Structure):      # orv_came_t
     _fields_ = ([(n, c_void_p) for n in ("p", "lo", "g", "m", "r", "c", "res_r", "res_c", "v")]
                 + [(n, c_long) for n in ("n", "n_rows", "n_cols", "n_v")]
@@ -189,6 +193,10 @@ SIGNATURES = {
     "orv_step_cache_probe": (c_int, [c_void_p] * 6 + [c_long, c_void_p] + [c_int] * 4 + [c_void_p]),
     "orv_step_cache_store": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "orv_step_cache_apply": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "orv_snapshot_chunk_bytes": (c_int, []),
+    "orv_snapshot_scratch_bytes": (c_long, [c_int, c_long]),
+    "orv_snapshot": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "orv_checksum": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_void_p]),
 }
 
 _lib = None

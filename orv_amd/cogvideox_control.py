@@ -608,12 +608,14 @@ class CogVideoXTransformer3DModelTraj(nn.Module, _lora.LoraMixin):
 
     def save_pretrained(self, save_directory, is_main_process: bool = True, save_function: Optional[Callable] = None,
                         safe_serialization: bool = True, variant: Optional[str] = None,
-                        max_shard_size: Union[int, str] = "5GB", push_to_hub: bool = False, **kwargs):
+                        max_shard_size: Union[int, str] = "5GB", push_to_hub: bool = False, state_dict=None, **kwargs):
+        """``state_dict``: the tensors to write in place of ``self.state_dict()`` (same keys; orv_amd.train_state passes the copies its
+        snapshot took, so that the file holds the weights of the save and not of whenever the writer gets to them)."""
         from .checkpoint import save_state_dict_dir
         if not is_main_process:
             return
         os.makedirs(save_directory, exist_ok=True)
-        save_state_dict_dir(self.state_dict(), save_directory, max_shard_size=max_shard_size)
+        save_state_dict_dir(self.state_dict() if state_dict is None else state_dict, save_directory, max_shard_size=max_shard_size)
         cfg = {**dict(self.config), "_class_name": "CogVideoXTransformer3DModelTraj", "_diffusers_version": "0.32.0.dev0"}
         with open(os.path.join(save_directory, self.config_name), "w", encoding="utf-8") as f:
             json.dump(cfg, f, indent=2)

@@ -399,14 +399,17 @@ class LoraMixin:
             sd[f"{name}.lora_B.weight"] = B.detach()
         return sd
 
-    def save_lora_adapter(self, save_directory, adapter_name: str = "default", prefix: str = "transformer"):
+    def save_lora_adapter(self, save_directory, adapter_name: str = "default", prefix: str = "transformer", state_dict=None):
+        """``state_dict``: the tensors to write in place of ``get_adapter_state_dict(adapter_name)`` (same keys; orv_amd.train_state passes
+        the copies its snapshot took)."""
         from safetensors.torch import save_file
         ad = self._lora_adapters.get(adapter_name)
         if ad is None:
             raise ValueError(f"no adapter named {adapter_name!r}")
         os.makedirs(save_directory, exist_ok=True)
         pre = prefix + "." if prefix else ""
-        sd = {pre + k: v.detach().to("cpu").contiguous() for k, v in self.get_adapter_state_dict(adapter_name).items()}
+        own = self.get_adapter_state_dict(adapter_name) if state_dict is None else state_dict
+        sd = {pre + k: v.detach().to("cpu").contiguous() for k, v in own.items()}
         meta = {"format": "pt", "lora_adapter_metadata": json.dumps(
             {"r": ad.r, "lora_alpha": ad.lora_alpha, "use_rslora": ad.use_rslora, "target_modules": ad.targets}, sort_keys=True)}
         path = os.path.join(save_directory, LORA_WEIGHT_NAME)

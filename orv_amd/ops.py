@@ -1502,3 +1502,81 @@ def step_cache_apply(x, t, B, Nt, Nv, D):
     with _timed(("step_cache_apply", B, Nv, D)):
         check(lib().orv_step_cache_apply(_p(x), _p(t), B, Nt, Nv, D, _stream()), "orv_step_cache_apply")
     return x
+
+
+# ---- training-state snapshot and checksums (csrc/snapshot.hip) ----
+def snapshot_chunk_bytes() -> int:
+    """Bytes per chunk of the snapshot kernels (an entry is processed in pieces of this size)."""
+    return int(lib().orv_snapshot_chunk_bytes())
+
+
+def _snapshot_call(fn, what, tensors, copies):
+    """One table launch over ``tensors`` (``copies[i]``: the destination of entry i, or None to sum it only) -> int64 [n, 2] on the device:
+    the u64 pairs (s1, s2), as bit patterns (torch has no arithmetic on uint64; ``sums_to_ints`` reads them)."""
+    import numpy as np
+    dev = tensors[0].device
+    for i, (t, c) in enumerate(zip(tensors, copies)):
+        for x, name in ((t, f"tensors[{i}]"), (c, f"copies[{i}]")):
+            if x is None:
+                continue
+            if not x.is_cuda or x.device != dev:
+                raise RuntimeError(f"orv_amd.ops: {what}: `{name}` must live on the GPU of the first tensor ({dev}; got {x.device}); there is no CPU path")
+            if not x.is_contiguous():
+                raise RuntimeError(f"orv_amd.ops: {what}: `{name}` must be contiguous")
+            if x.data_ptr() % 4:
+                raise RuntimeError(f"orv_amd.ops: {what}: `{name}` must start at a 4-byte aligned address")
+    nbytes = [t.numel() * t.element_size() for t in tensors]
+    n = len(tensors)
+    table = np.zeros((n, 3), dtype=np.int64)
+    table[:, 0] = [t.data_ptr() if b else 0 for t, b in zip(tensors, nbytes)]
+    table[:, 1] = [c.data_ptr() if c is not None and b else 0 for c, b in zip(copies, nbytes)]
+    table[:, 2] = nbytes
+    host = torch.from_numpy(table).pin_memory()          # read by the library now (validation) and by the copy engine on the stream
+    entries = host.to(dev, non_blocking=True)
+    need = lib().orv_snapshot_scratch_bytes(n, int(sum(nbytes)))
+    if need < 0:
+        check(1, "orv_snapshot_scratch_bytes")
+    scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)
+    sums = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    with _timed((what, n, int(sum(nbytes)))):
+        check(fn(_p(entries), host.data_ptr(), n, _p(sums), _p(scratch), scratch.numel(), _stream()), what)
+    return sums
+
+
+def snapshot_into(tensors, copies):
+    """``snapshot`` into destinations of the caller: ``copies[i]`` receives ``tensors[i]`` (None: summed only) and must hold as many bytes;
+    any 4-byte aligned address is taken, independently of the source's.  -> ``sums``."""
+    tensors, copies = list(tensors), list(copies)
+    if len(tensors) != len(copies) or not tensors:
+        raise ValueError(f"orv_amd.ops: snapshot_into: {len(copies)} destinations for {len(tensors)} tensors (at least one)")
+    for i, (t, c) in enumerate(zip(tensors, copies)):
+        if c is not None and c.numel() * c.element_size() != t.numel() * t.element_size():
+            raise ValueError(f"orv_amd.ops: snapshot_into: `copies[{i}]` holds another number of bytes than `tensors[{i}]`")
+    return _snapshot_call(lib().orv_snapshot, "orv_snapshot", tensors, copies)
+
+
+def snapshot(tensors, copy=None):
+    """Copy every tensor of the list into a new tensor and checksum it, all in one table launch plus one combine launch on the current stream
+    (``orv_snapshot``) -> ``(copies, sums)``.  ``copy``: optional list of booleans; an entry with False is summed only and its copy is None.
+    ``sums`` is int64 [n, 2] on the device (``sums_to_ints``).  Contiguous GPU tensors of any dtype, 4-byte aligned, on one device."""
+    tensors = list(tensors)
+    if not tensors:
+        return [], torch.empty((0, 2), dtype=torch.int64)
+    flags = [True] * len(tensors) if copy is None else [bool(c) for c in copy]
+    if len(flags) != len(tensors):
+        raise ValueError(f"orv_amd.ops: snapshot: {len(flags)} copy flags for {len(tensors)} tensors")
+    copies = [torch.empty_like(t, memory_format=torch.contiguous_format) if f and t.is_cuda else None for t, f in zip(tensors, flags)]
+    return copies, snapshot_into(tensors, copies)
+
+
+def checksum(tensors):
+    """``sums`` of ``snapshot`` without a copy (``orv_checksum``): nothing but the sums is written."""
+    tensors = list(tensors)
+    if not tensors:
+        return torch.empty((0, 2), dtype=torch.int64)
+    return _snapshot_call(lib().orv_checksum, "orv_checksum", tensors, [None] * len(tensors))
+
+
+def sums_to_ints(sums):
+    """int64 [n, 2] (device or host) -> list of (s1, s2) Python ints in [0, 2^64).  Synchronises with the stream that wrote ``sums``."""
+    return [(int(a) & 0xFFFFFFFFFFFFFFFF, int(b) & 0xFFFFFFFFFFFFFFFF) for a, b in sums.cpu().tolist()]
