@@ -308,6 +308,46 @@ int orv_adamw_flat_s8(void* p, const void* g, unsigned char* m8, unsigned char* 
                       const long* seg_start, const unsigned char* seg_active, const int* seg_step, int nseg, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int step, const float* clip_coef, void* lo, int mode, unsigned seed,
                       void* stream);          /* mode 0 / 1 / 2 as orv_adamw_flat_ex; mode 0 here = nearest-even bf16 */
+/* Parameter groups on the flat layout (FusedAdamW(param groups)).  seg_group[nseg] (device bytes) names the group of
+ * every segment; the table of the groups' two numbers travels BY VALUE with the launch, so a schedule changes any group's rate at every
+ * step with no host-to-device copy and no device table to keep in sync.  Every seg_group value must be < ngroups (the caller builds the
+ * table and checks it there; the kernels leave a segment whose byte is >= 8 untouched). */
+#define ORV_ADAMW_MAX_GROUPS 8
+typedef struct {
+    int ngroups;                                  /* 1..ORV_ADAMW_MAX_GROUPS */
+    float lr[ORV_ADAMW_MAX_GROUPS];
+    float weight_decay[ORV_ADAMW_MAX_GROUPS];
+} orv_adamw_groups_t;
+/* orv_adamw_flat_ex / orv_adamw_flat_s8 with the scalars lr and weight_decay replaced by (seg_group, groups): a segment's update is exactly
+ * the parent's formula, in the same operation order (the same device function), with its group's two numbers - the group is looked up once
+ * per workgroup, which never straddles a segment.  All three modes; inactive segments keep every byte.  A null buffer, ngroups outside
+ * 1..8 or n % 2048 != 0 return non-zero with an orv_last_error message before anything is launched.
+ * orv_adamw_flat_s8_groups has one argument more, common_count: the per-segment count that most segments are at (<= 0: `step`).  The fp8
+ * kernel takes the host's bias corrections for a segment whose count equals it and works out its own (two powf per lane, a third more
+ * kernel time) for any other; `step` seeds the rounding and keeps advancing over a skipped step, the counts do not, so after a skip the
+ * caller passes the count they stopped at.  The result does not depend on it. */
+int orv_adamw_flat_groups(void* p, const void* g, float* m, float* v, long n, const long* seg_start, const unsigned char* seg_active,
+                          const int* seg_step, int nseg, const unsigned char* seg_group, orv_adamw_groups_t groups, float beta1,
+                          float beta2, float eps, int step, const float* clip_coef, void* lo, int mode, unsigned seed, void* stream);
+int orv_adamw_flat_s8_groups(void* p, const void* g, unsigned char* m8, unsigned char* v8, unsigned char* m_exp, unsigned char* v_exp,
+                             long n, const long* seg_start, const unsigned char* seg_active, const int* seg_step, int nseg,
+                             const unsigned char* seg_group, orv_adamw_groups_t groups, float beta1, float beta2, float eps, int step,
+                             int common_count, const float* clip_coef, void* lo, int mode, unsigned seed, void* stream);
+/* out[i] = sum of g^2 over segment i = elements [seg_start[i], seg_start[i + 1]) of the bf16 buffer g (seg_start int64[nseg + 1] on the
+ * device, multiples of 8), in fp64, for all nseg segments in ONE launch, one workgroup per segment, no atomics.  The order of the
+ * additions is fixed by the segment's length alone (stated in orv_amd/csrc/optim_groups.hip; restated in numpy in
+ * tests/adamw_groups_ref.py): two runs give the same bits, and a non-finite element makes its own segment's sum non-finite and nothing
+ * else. */
+int orv_segment_sumsq(const void* g, const long* seg_start, int nseg, double* out, void* stream);
+#define ORV_GUARD_REPORT 11      /* doubles in `report`: [0] ss, [1..8] one sum per group, [9] running skip count, [10] skipped (0 / 1) */
+/* The decisions of one optimizer step, on the device, in one launch of one workgroup (operation order in optim_groups.hip):
+ *   ss = seg_ss[0] + seg_ss[1] + ... in index order (fp64); report[1 + j] the same over the segments of group j;
+ *   *clip_coef = fp32(c * inv_world), c = max_grad_norm / (sqrt(ss) * inv_world + 1e-6) where that is below 1, else 1 (a NaN stays a NaN;
+ *                max_grad_norm == 0: c = 1, no clipping), all in fp64;
+ *   skip_nonfinite != 0 and ss not finite: every byte of seg_active is cleared, report[9] += 1, report[10] = 1 and *clip_coef = 0;
+ *   otherwise report[10] = 0.  report[9] is read and written, so the caller zeroes `report` once. */
+int orv_step_guard(const double* seg_ss, const unsigned char* seg_group, int nseg, float max_grad_norm, float inv_world,
+                   int skip_nonfinite, unsigned char* seg_active, float* clip_coef, double* report, void* stream);
 /* x fp32[n] -> exactly the bytes orv_adamw_flat_s8 would store for the fp32 moments x at that (seed, step, flat index), and back
  * (exact).  format 0 = first moment (e4m3fn), 1 = second moment (e5m2); n % 256 == 0. */
 int orv_state8_quantize(const float* x, unsigned char* q, unsigned char* exps, long n, int format, unsigned seed, int step, void* stream);

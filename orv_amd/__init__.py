@@ -23,7 +23,7 @@ def install(verbose: bool = False):
 
 def __getattr__(name):
     # the optimizer surface of the train scripts, resolved on first use (importing the package stays free of torch)
-    if name in ("FusedProdigy", "FusedCAME", "get_optimizer"):
+    if name in ("FusedProdigy", "FusedCAME", "get_optimizer", "named_groups"):
         from . import optim
         return getattr(optim, name)
     # the weight average to sample from (orv_amd/ema.py), resolved on first use likewise

@@ -43,6 +43,13 @@ class SnapshotEntry(Structure):      # orv_snapshot_entry_t
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("bytes", c_long)]
 
 
+ADAMW_MAX_GROUPS = 8        # ORV_ADAMW_MAX_GROUPS
+
+
+class AdamwGroups(Structure):      # orv_adamw_groups_t, passed by value
+    _fields_ = [("ngroups", c_int), ("lr", c_float * ADAMW_MAX_GROUPS), ("weight_decay", c_float * ADAMW_MAX_GROUPS)]
+
+
 class Came(Structure):      # orv_came_t
     _fields_ = ([(n, c_void_p) for n in ("p", "lo", "g", "m", "r", "c", "res_r", "res_c", "v")]
                 + [(n, c_long) for n in ("n", "n_rows", "n_cols", "n_v")]
@@ -128,6 +135,13 @@ SIGNATURES = {
                                   c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_uint, c_void_p]),
     "orv_adamw_flat_s8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int,
                                   c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_uint, c_void_p]),
+    "orv_adamw_flat_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                      AdamwGroups, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_int, c_uint, c_void_p]),
+    "orv_adamw_flat_s8_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                                         c_int, c_void_p, AdamwGroups, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p, c_int,
+                                         c_uint, c_void_p]),
+    "orv_segment_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "orv_step_guard": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "orv_state8_quantize": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_uint, c_int, c_void_p]),
     "orv_state8_dequantize": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]),
     "orv_prodigy_moments": (c_int, [c_void_p] * 7 + [c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float,

@@ -631,16 +631,27 @@ __global__ void adamw_kernel(bf16_t* __restrict__ p, const bf16_t* __restrict__ 
 // ---- the same update over ONE flat buffer holding every parameter (segments padded to 2048 elements): a workgroup owns
 //      2048 consecutive elements = one segment; segments whose parameter had no gradient this step are skipped
 //      (torch.optim semantics: no decay, no moment update).  16-byte accesses throughout (22 bytes of traffic per element).
-__global__ __launch_bounds__(256) void adamw_flat_kernel(bf16_t* __restrict__ p, const bf16_t* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v,
-                                                         const long* __restrict__ seg_start, const uint8_t* __restrict__ active,
-                                                         int nseg, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                         float bc2, const float* __restrict__ clip,
-                                                         const int* __restrict__ seg_step) {
+//      GROUPS: lr and wd are those of the segment's parameter group (orv_adamw_flat_groups mode 0), picked once per workgroup with scalar
+//      selects from the by-value table; everything else is the one body, so the two kernels agree bit for bit.
+template <bool GROUPS>
+__device__ __forceinline__ void adamw_flat_body(bf16_t* __restrict__ p, const bf16_t* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, const long* __restrict__ seg_start,
+                                                const uint8_t* __restrict__ active, int nseg, float lr, float b1, float b2, float eps,
+                                                float wd, float bc1, float bc2, const float* __restrict__ clip,
+                                                const int* __restrict__ seg_step, const uint8_t* __restrict__ seg_group,
+                                                const orv_adamw_groups_t& groups) {
     const long e0 = (long)blockIdx.x * 2048;
     int lo = 0, hi = nseg - 1;                 // last segment with seg_start <= e0 (wave-uniform binary search)
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg_start[mid] <= e0) lo = mid; else hi = mid - 1; }
-    if (!active[lo]) return;
+    // the group byte decides the branch together with the activity byte (a group outside the table: the segment is left alone), so the
+    // two loads are in flight together instead of one behind the other
+    const int gi = GROUPS ? seg_group[lo] : 0;
+    if (!active[lo] | (gi >= ORV_ADAMW_MAX_GROUPS)) return;
+    if (GROUPS) {
+#pragma unroll
+        for (int j = 0; j < ORV_ADAMW_MAX_GROUPS; ++j)
+            if (gi == j) { lr = groups.lr[j]; wd = groups.weight_decay[j]; }
+    }
     if (seg_step) {                            // torch.optim.AdamW keeps one step count PER PARAMETER (bias correction)
         const float st = (float)seg_step[lo];
         bc1 = 1.f - powf(b1, st);
@@ -665,6 +676,26 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(bf16_t* __restrict__ p,
     *(float4*)(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]); *(float4*)(m + i + 4) = make_float4(mm[4], mm[5], mm[6], mm[7]);
     *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]); *(float4*)(v + i + 4) = make_float4(vv[4], vv[5], vv[6], vv[7]);
     *(uint4*)(p + i) = make_uint4(pack2bf(pv[0], pv[1]), pack2bf(pv[2], pv[3]), pack2bf(pv[4], pv[5]), pack2bf(pv[6], pv[7]));
+}
+
+__global__ __launch_bounds__(256) void adamw_flat_kernel(bf16_t* __restrict__ p, const bf16_t* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v,
+                                                         const long* __restrict__ seg_start, const uint8_t* __restrict__ active,
+                                                         int nseg, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                         float bc2, const float* __restrict__ clip,
+                                                         const int* __restrict__ seg_step) {
+    adamw_flat_body<false>(p, g, m, v, seg_start, active, nseg, lr, b1, b2, eps, wd, bc1, bc2, clip, seg_step, nullptr,
+                           orv_adamw_groups_t{});
+}
+
+__global__ __launch_bounds__(256) void adamw_flat_groups_kernel(bf16_t* __restrict__ p, const bf16_t* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v,
+                                                                const long* __restrict__ seg_start,
+                                                                const uint8_t* __restrict__ active, int nseg, float b1, float b2,
+                                                                float eps, float bc1, float bc2, const float* __restrict__ clip,
+                                                                const int* __restrict__ seg_step,
+                                                                const uint8_t* __restrict__ seg_group, const orv_adamw_groups_t groups) {
+    adamw_flat_body<true>(p, g, m, v, seg_start, active, nseg, 0.f, b1, b2, eps, 0.f, bc1, bc2, clip, seg_step, seg_group, groups);
 }
 
 // ---- out[0] += sum g^2 (global gradient norm)
@@ -856,6 +887,20 @@ extern "C" int orv_adamw_flat_steps(void* p, const void* g, float* m, float* v, 
                        (const bf16_t*)g, m, v, seg_start, seg_active, nseg, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
                        clip_coef, seg_step);
     return orv_check_launch("orv_adamw_flat");
+}
+
+int orv_adamw_flat_groups_bf16(void* p, const void* g, float* m, float* v, long n, const long* seg_start, const unsigned char* seg_active,
+                               const int* seg_step, int nseg, const unsigned char* seg_group, orv_adamw_groups_t groups, float beta1,
+                               float beta2, float eps, int step, const float* clip_coef, void* stream) {
+    ORV_REQUIRE(p && g && m && v && seg_start && seg_active && seg_group && nseg > 0 && step > 0, "orv_adamw_flat_groups: bad arguments");
+    ORV_REQUIRE(groups.ngroups >= 1 && groups.ngroups <= ORV_ADAMW_MAX_GROUPS, "orv_adamw_flat_groups: ngroups=%d (supported: 1..%d)",
+                groups.ngroups, ORV_ADAMW_MAX_GROUPS);
+    ORV_REQUIRE(n > 0 && n % 2048 == 0, "orv_adamw_flat_groups: n=%ld must be a multiple of 2048 (pad every segment)", n);
+    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    hipLaunchKernelGGL(adamw_flat_groups_kernel, dim3((unsigned)(n / 2048)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p,
+                       (const bf16_t*)g, m, v, seg_start, seg_active, nseg, beta1, beta2, eps, bc1, bc2, clip_coef, seg_step, seg_group,
+                       groups);
+    return orv_check_launch("orv_adamw_flat_groups");
 }
 
 extern "C" int orv_adamw_flat(void* p, const void* g, float* m, float* v, long n, const long* seg_start,

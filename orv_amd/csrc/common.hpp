@@ -17,6 +17,13 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 void orv_set_error(const char* fmt, ...);
 int orv_check_launch(const char* what);
 
+// mode 0 of orv_adamw_flat_groups: the plain bf16 update lives beside its parent kernel in backward.hip (library-internal, not exported)
+__attribute__((visibility("hidden"))) int orv_adamw_flat_groups_bf16(void* p, const void* g, float* m, float* v, long n,
+                                                                     const long* seg_start, const unsigned char* seg_active,
+                                                                     const int* seg_step, int nseg, const unsigned char* seg_group,
+                                                                     orv_adamw_groups_t groups, float beta1, float beta2, float eps, int step,
+                                                                     const float* clip_coef, void* stream);
+
 #define ORV_REQUIRE(cond, ...)                 \
     do {                                       \
         if (!(cond)) {                         \

@@ -45,18 +45,27 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
 
 // MODE 1: split fp32 master (p + lo, 26 bytes of traffic per element); MODE 2: stochastic rounding (22 bytes).
 // A workgroup owns 2048 consecutive elements = part of one segment, 8 per lane, 16-byte accesses (lo: one 16-byte access per lane).
-template <int MODE>
-__global__ __launch_bounds__(256) void adamw_flat_ex_kernel(bf16_t* __restrict__ p, int16_t* __restrict__ lo16,
-                                                            const bf16_t* __restrict__ g, float* __restrict__ m,
-                                                            float* __restrict__ v, const long* __restrict__ seg_start,
-                                                            const uint8_t* __restrict__ active, int nseg, float lr, float b1,
-                                                            float b2, float eps, float wd, float bc1, float bc2,
-                                                            const float* __restrict__ clip, const int* __restrict__ seg_step,
-                                                            uint32_t seed, uint32_t step) {
+// GROUPS: lr and wd are those of the segment's parameter group (orv_adamw_flat_groups), picked once per workgroup - a workgroup never
+// straddles a segment - from the by-value table with scalar selects (no indexed access, so the table never leaves the kernel arguments).
+template <int MODE, bool GROUPS>
+__device__ __forceinline__ void adamw_flat_ex_body(bf16_t* __restrict__ p, int16_t* __restrict__ lo16, const bf16_t* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, const long* __restrict__ seg_start,
+                                                   const uint8_t* __restrict__ active, int nseg, float lr, float b1, float b2, float eps,
+                                                   float wd, float bc1, float bc2, const float* __restrict__ clip,
+                                                   const int* __restrict__ seg_step, uint32_t seed, uint32_t step,
+                                                   const uint8_t* __restrict__ seg_group, const orv_adamw_groups_t& groups) {
     const long e0 = (long)blockIdx.x * 2048;
     int lo = 0, hi = nseg - 1;                 // last segment with seg_start <= e0 (wave-uniform binary search)
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg_start[mid] <= e0) lo = mid; else hi = mid - 1; }
-    if (!active[lo]) return;
+    // the group byte decides the branch together with the activity byte (a group outside the table: the segment is left alone), so the
+    // two loads are in flight together instead of one behind the other
+    const int gi = GROUPS ? seg_group[lo] : 0;
+    if (!active[lo] | (gi >= ORV_ADAMW_MAX_GROUPS)) return;
+    if (GROUPS) {
+#pragma unroll
+        for (int j = 0; j < ORV_ADAMW_MAX_GROUPS; ++j)
+            if (gi == j) { lr = groups.lr[j]; wd = groups.weight_decay[j]; }
+    }
     if (seg_step) {                            // one step count PER PARAMETER (bias correction), as in adamw_flat_kernel
         const float st = (float)seg_step[lo];
         bc1 = 1.f - powf(b1, st);
@@ -101,6 +110,31 @@ __global__ __launch_bounds__(256) void adamw_flat_ex_kernel(bf16_t* __restrict__
         *(uint4*)(lo16 + i) = make_uint4(nl[0] | nl[1] << 16, nl[2] | nl[3] << 16, nl[4] | nl[5] << 16, nl[6] | nl[7] << 16);
 }
 
+template <int MODE>
+__global__ __launch_bounds__(256) void adamw_flat_ex_kernel(bf16_t* __restrict__ p, int16_t* __restrict__ lo16,
+                                                            const bf16_t* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, const long* __restrict__ seg_start,
+                                                            const uint8_t* __restrict__ active, int nseg, float lr, float b1,
+                                                            float b2, float eps, float wd, float bc1, float bc2,
+                                                            const float* __restrict__ clip, const int* __restrict__ seg_step,
+                                                            uint32_t seed, uint32_t step) {
+    adamw_flat_ex_body<MODE, false>(p, lo16, g, m, v, seg_start, active, nseg, lr, b1, b2, eps, wd, bc1, bc2, clip, seg_step, seed, step,
+                                    nullptr, orv_adamw_groups_t{});
+}
+
+// the same body; lr and weight decay per parameter group
+template <int MODE>
+__global__ __launch_bounds__(256) void adamw_flat_groups_kernel(bf16_t* __restrict__ p, int16_t* __restrict__ lo16,
+                                                                const bf16_t* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, const long* __restrict__ seg_start,
+                                                                const uint8_t* __restrict__ active, int nseg, float b1, float b2,
+                                                                float eps, float bc1, float bc2, const float* __restrict__ clip,
+                                                                const int* __restrict__ seg_step, uint32_t seed, uint32_t step,
+                                                                const uint8_t* __restrict__ seg_group, const orv_adamw_groups_t groups) {
+    adamw_flat_ex_body<MODE, true>(p, lo16, g, m, v, seg_start, active, nseg, 0.f, b1, b2, eps, 0.f, bc1, bc2, clip, seg_step, seed, step,
+                                   seg_group, groups);
+}
+
 }  // namespace
 
 extern "C" int orv_adamw_flat_ex(void* p, const void* g, float* m, float* v, long n, const long* seg_start,
@@ -125,4 +159,31 @@ extern "C" int orv_adamw_flat_ex(void* p, const void* g, float* m, float* v, lon
                            v, seg_start, seg_active, nseg, lr, beta1, beta2, eps, weight_decay, bc1, bc2, clip_coef, seg_step, seed,
                            (uint32_t)step);
     return orv_check_launch("orv_adamw_flat_ex");
+}
+
+extern "C" int orv_adamw_flat_groups(void* p, const void* g, float* m, float* v, long n, const long* seg_start,
+                                     const unsigned char* seg_active, const int* seg_step, int nseg, const unsigned char* seg_group,
+                                     orv_adamw_groups_t groups, float beta1, float beta2, float eps, int step, const float* clip_coef,
+                                     void* lo, int mode, unsigned seed, void* stream) {
+    ORV_REQUIRE(mode >= 0 && mode <= 2, "orv_adamw_flat_groups: mode=%d (0 bf16, 1 split_fp32, 2 stochastic)", mode);
+    ORV_REQUIRE(groups.ngroups >= 1 && groups.ngroups <= ORV_ADAMW_MAX_GROUPS, "orv_adamw_flat_groups: ngroups=%d (supported: 1..%d)",
+                groups.ngroups, ORV_ADAMW_MAX_GROUPS);
+    ORV_REQUIRE(seg_group, "orv_adamw_flat_groups: null seg_group (one group index per segment, on the device)");
+    if (mode == 0)                             // the plain bf16 update lives beside its parent kernel (backward.hip)
+        return orv_adamw_flat_groups_bf16(p, g, m, v, n, seg_start, seg_active, seg_step, nseg, seg_group, groups, beta1, beta2, eps, step,
+                                           clip_coef, stream);
+    ORV_REQUIRE(p && g && m && v && seg_start && seg_active && nseg > 0 && step > 0, "orv_adamw_flat_groups: bad arguments");
+    ORV_REQUIRE(n > 0 && n % 2048 == 0, "orv_adamw_flat_groups: n=%ld must be a multiple of 2048 (pad every segment)", n);
+    ORV_REQUIRE(mode != 1 || lo, "orv_adamw_flat_groups: mode 1 (split_fp32) needs the low-half buffer lo (int16[n])");
+    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    const dim3 grid((unsigned)(n / 2048)), block(256);
+    if (mode == 1)
+        hipLaunchKernelGGL(adamw_flat_groups_kernel<1>, grid, block, 0, (hipStream_t)stream, (bf16_t*)p, (int16_t*)lo, (const bf16_t*)g, m,
+                           v, seg_start, seg_active, nseg, beta1, beta2, eps, bc1, bc2, clip_coef, seg_step, seed, (uint32_t)step,
+                           seg_group, groups);
+    else
+        hipLaunchKernelGGL(adamw_flat_groups_kernel<2>, grid, block, 0, (hipStream_t)stream, (bf16_t*)p, (int16_t*)nullptr,
+                           (const bf16_t*)g, m, v, seg_start, seg_active, nseg, beta1, beta2, eps, bc1, bc2, clip_coef, seg_step, seed,
+                           (uint32_t)step, seg_group, groups);
+    return orv_check_launch("orv_adamw_flat_groups");
 }

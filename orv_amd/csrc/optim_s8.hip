@@ -163,22 +163,33 @@ __device__ __forceinline__ void s8_decode8(uint2 q, int e, float* out) {
 
 // MODE 0: nearest-even bf16 weight; 1: split fp32 master (p + lo); 2: stochastic rounding of the weight.  10 + 2/256 bytes of traffic
 // per element in modes 0 and 2 (14 in mode 1) against the 22 of the fp32-moment kernels.
-template <int MODE>
-__global__ __launch_bounds__(256) void adamw_flat_s8_kernel(bf16_t* __restrict__ p, int16_t* __restrict__ lo16,
-                                                            const bf16_t* __restrict__ g, uint8_t* __restrict__ m8,
-                                                            uint8_t* __restrict__ v8, uint8_t* __restrict__ m_exp,
-                                                            uint8_t* __restrict__ v_exp, const long* __restrict__ seg_start,
-                                                            const uint8_t* __restrict__ active, int nseg, float lr, float b1,
-                                                            float b2, float eps, float wd, float bc1, float bc2,
-                                                            const float* __restrict__ clip, const int* __restrict__ seg_step,
-                                                            uint32_t seed, uint32_t step) {
+// GROUPS: lr and wd are those of the segment's parameter group (orv_adamw_flat_s8_groups), picked once per workgroup with scalar selects
+// from the by-value table, as in optim.hip.
+template <int MODE, bool GROUPS>
+__device__ __forceinline__ void adamw_flat_s8_body(bf16_t* __restrict__ p, int16_t* __restrict__ lo16, const bf16_t* __restrict__ g,
+                                                   uint8_t* __restrict__ m8, uint8_t* __restrict__ v8, uint8_t* __restrict__ m_exp,
+                                                   uint8_t* __restrict__ v_exp, const long* __restrict__ seg_start,
+                                                   const uint8_t* __restrict__ active, int nseg, float lr, float b1, float b2, float eps,
+                                                   float wd, float bc1, float bc2, const float* __restrict__ clip,
+                                                   const int* __restrict__ seg_step, uint32_t seed, uint32_t step,
+                                                   uint32_t common, const uint8_t* __restrict__ seg_group,
+                                                   const orv_adamw_groups_t& groups) {
     const long e0 = (long)blockIdx.x * 2048;
     int lo = 0, hi = nseg - 1;                 // last segment with seg_start <= e0 (workgroup-uniform binary search)
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg_start[mid] <= e0) lo = mid; else hi = mid - 1; }
-    if (!active[lo]) return;                   // uniform: every lane of a live wave reaches the cross-lane reductions below
+    // the group byte decides the branch together with the activity byte (a group outside the table: the segment is left alone), so the
+    // two loads are in flight together instead of one behind the other
+    const int gi = GROUPS ? seg_group[lo] : 0;
+    if (!active[lo] | (gi >= ORV_ADAMW_MAX_GROUPS)) return;                   // uniform: every lane of a live wave reaches the cross-lane reductions below
+    if (GROUPS) {
+#pragma unroll
+        for (int j = 0; j < ORV_ADAMW_MAX_GROUPS; ++j)
+            if (gi == j) { lr = groups.lr[j]; wd = groups.weight_decay[j]; }
+    }
     // one step count PER PARAMETER (bias correction), as in adamw_flat_kernel; a segment at the global count (the common case) takes the
     // host's corrections: two powf per lane are a fifth of this kernel's arithmetic, and the arithmetic, not the memory, bounds it
-    if (seg_step && (uint32_t)seg_step[lo] != step) {
+    // (`common` is the count bc1 / bc2 were made for: `step` itself in the parent; behind it after a skipped step, orv_adamw_flat_s8_groups)
+    if (seg_step && (uint32_t)seg_step[lo] != common) {
         const float st = (float)seg_step[lo];
         bc1 = 1.f - powf(b1, st);
         bc2 = 1.f - powf(b2, st);
@@ -240,6 +251,34 @@ __global__ __launch_bounds__(256) void adamw_flat_s8_kernel(bf16_t* __restrict__
         m_exp[blk] = (uint8_t)(em + 127);
         v_exp[blk] = (uint8_t)(ev + 127);
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void adamw_flat_s8_kernel(bf16_t* __restrict__ p, int16_t* __restrict__ lo16,
+                                                            const bf16_t* __restrict__ g, uint8_t* __restrict__ m8,
+                                                            uint8_t* __restrict__ v8, uint8_t* __restrict__ m_exp,
+                                                            uint8_t* __restrict__ v_exp, const long* __restrict__ seg_start,
+                                                            const uint8_t* __restrict__ active, int nseg, float lr, float b1,
+                                                            float b2, float eps, float wd, float bc1, float bc2,
+                                                            const float* __restrict__ clip, const int* __restrict__ seg_step,
+                                                            uint32_t seed, uint32_t step) {
+    adamw_flat_s8_body<MODE, false>(p, lo16, g, m8, v8, m_exp, v_exp, seg_start, active, nseg, lr, b1, b2, eps, wd, bc1, bc2, clip,
+                                    seg_step, seed, step, step, nullptr, orv_adamw_groups_t{});
+}
+
+// the same body; lr and weight decay per parameter group
+template <int MODE>
+__global__ __launch_bounds__(256) void adamw_flat_s8_groups_kernel(bf16_t* __restrict__ p, int16_t* __restrict__ lo16,
+                                                                   const bf16_t* __restrict__ g, uint8_t* __restrict__ m8,
+                                                                   uint8_t* __restrict__ v8, uint8_t* __restrict__ m_exp,
+                                                                   uint8_t* __restrict__ v_exp, const long* __restrict__ seg_start,
+                                                                   const uint8_t* __restrict__ active, int nseg, float b1, float b2,
+                                                                   float eps, float bc1, float bc2, const float* __restrict__ clip,
+                                                                   const int* __restrict__ seg_step, uint32_t seed, uint32_t step,
+                                                                   uint32_t common, const uint8_t* __restrict__ seg_group,
+                                                                   const orv_adamw_groups_t groups) {
+    adamw_flat_s8_body<MODE, true>(p, lo16, g, m8, v8, m_exp, v_exp, seg_start, active, nseg, 0.f, b1, b2, eps, 0.f, bc1, bc2, clip,
+                                   seg_step, seed, step, common, seg_group, groups);
 }
 
 // fp32 -> the bytes adamw_flat_s8_kernel stores for these values at (seed, step, flat index); n % 256 == 0, so a block of 32 lanes is
@@ -304,6 +343,33 @@ extern "C" int orv_adamw_flat_s8(void* p, const void* g, unsigned char* m8, unsi
     else ORV_S8_LAUNCH(2, nullptr);
 #undef ORV_S8_LAUNCH
     return orv_check_launch("orv_adamw_flat_s8");
+}
+
+extern "C" int orv_adamw_flat_s8_groups(void* p, const void* g, unsigned char* m8, unsigned char* v8, unsigned char* m_exp,
+                                        unsigned char* v_exp, long n, const long* seg_start, const unsigned char* seg_active,
+                                        const int* seg_step, int nseg, const unsigned char* seg_group, orv_adamw_groups_t groups,
+                                        float beta1, float beta2, float eps, int step, int common_count, const float* clip_coef,
+                                        void* lo, int mode, unsigned seed, void* stream) {
+    ORV_REQUIRE(mode >= 0 && mode <= 2, "orv_adamw_flat_s8_groups: mode=%d (0 bf16, 1 split_fp32, 2 stochastic)", mode);
+    ORV_REQUIRE(groups.ngroups >= 1 && groups.ngroups <= ORV_ADAMW_MAX_GROUPS, "orv_adamw_flat_s8_groups: ngroups=%d (supported: 1..%d)",
+                groups.ngroups, ORV_ADAMW_MAX_GROUPS);
+    ORV_REQUIRE(p && g && m8 && v8 && m_exp && v_exp && seg_start && seg_active && seg_group && nseg > 0 && step > 0,
+                "orv_adamw_flat_s8_groups: bad arguments");
+    ORV_REQUIRE(n > 0 && n % 2048 == 0, "orv_adamw_flat_s8_groups: n=%ld must be a multiple of 2048 (pad every segment)", n);
+    ORV_REQUIRE(mode != 1 || lo, "orv_adamw_flat_s8_groups: mode 1 (split_fp32) needs the low-half buffer lo (int16[n])");
+    // the host's bias corrections serve the segments at `common`: the global step, or the count the caller knows most segments are at
+    const int common = common_count > 0 ? common_count : step;
+    const float bc1 = 1.f - powf(beta1, (float)common), bc2 = 1.f - powf(beta2, (float)common);
+    const dim3 grid((unsigned)(n / 2048)), block(256);
+#define ORV_S8G_LAUNCH(MODE, LO)                                                                                                        \
+    hipLaunchKernelGGL(adamw_flat_s8_groups_kernel<MODE>, grid, block, 0, (hipStream_t)stream, (bf16_t*)p, (int16_t*)(LO),              \
+                       (const bf16_t*)g, m8, v8, m_exp, v_exp, seg_start, seg_active, nseg, beta1, beta2, eps, bc1, bc2, clip_coef,     \
+                       seg_step, seed, (uint32_t)step, (uint32_t)common, seg_group, groups)
+    if (mode == 0) ORV_S8G_LAUNCH(0, nullptr);
+    else if (mode == 1) ORV_S8G_LAUNCH(1, lo);
+    else ORV_S8G_LAUNCH(2, nullptr);
+#undef ORV_S8G_LAUNCH
+    return orv_check_launch("orv_adamw_flat_s8_groups");
 }
 
 extern "C" int orv_state8_quantize(const float* x, unsigned char* q, unsigned char* exps, long n, int format, unsigned seed, int step,

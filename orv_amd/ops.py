@@ -12,7 +12,8 @@ import ctypes
 import os
 import torch
 
-from ._lib import Gemm, Groups, RowMap, check, lib
+from ._lib import ADAMW_MAX_GROUPS as _ADAMW_MAX_GROUPS
+from ._lib import AdamwGroups, Gemm, Groups, RowMap, check, lib
 
 BF16 = torch.bfloat16
 ACT = {None: 0, "none": 0, "silu": 1, "gelu_tanh": 2}
@@ -760,6 +761,112 @@ def adamw_flat_s8(p, g, m8, v8, m_exp, v_exp, seg_start, seg_active, lr, beta1, 
                                   _p(seg_step), seg_active.numel(), float(lr), float(beta1), float(beta2), float(eps),
                                   float(weight_decay), int(step), _p(clip_coef), _p(lo), int(mode), int(seed) & 0xFFFFFFFF, _stream()),
           "orv_adamw_flat_s8")
+
+
+ADAMW_MAX_GROUPS = _ADAMW_MAX_GROUPS
+GUARD_REPORT = ("ss",) + tuple(f"group{j}" for j in range(ADAMW_MAX_GROUPS)) + ("skip_count", "skipped")      # the fp64[11] of orv_step_guard
+
+
+def _adamw_groups(seg_group, seg_active, lrs, weight_decays, max_group=None):
+    """The by-value table of ``orv_adamw_flat_groups`` from two equally long sequences; ``max_group`` is the largest value in ``seg_group``
+    as the caller knows it from building that table on the host (``None``: read it from the device, one host sync - tests and tools)."""
+    lrs, weight_decays = [float(x) for x in lrs], [float(x) for x in weight_decays]
+    if not 1 <= len(lrs) <= ADAMW_MAX_GROUPS or len(weight_decays) != len(lrs):
+        raise RuntimeError(f"orv_amd.ops: {len(lrs)} learning rates and {len(weight_decays)} weight decays (supported: 1..{ADAMW_MAX_GROUPS} "
+                           "groups, one of each per group)")
+    _need(seg_group, torch.uint8, "seg_group")
+    if not seg_group.is_contiguous() or seg_group.numel() != seg_active.numel():
+        raise RuntimeError(f"orv_amd.ops: `seg_group` must be contiguous and hold one byte per segment ({seg_active.numel()})")
+    if max_group is None:
+        max_group = int(seg_group.max().item())
+    if max_group >= len(lrs):
+        raise RuntimeError(f"orv_amd.ops: `seg_group` names group {max_group}, the table holds {len(lrs)} (every value must be < ngroups)")
+    tab = AdamwGroups()
+    tab.ngroups = len(lrs)
+    for j, (a, b) in enumerate(zip(lrs, weight_decays)):
+        tab.lr[j], tab.weight_decay[j] = a, b
+    return tab
+
+
+def adamw_flat_groups(p, g, m, v, seg_start, seg_active, seg_group, lrs, weight_decays, beta1, beta2, eps, step, clip_coef=None,
+                      seg_step=None, lo=None, mode=0, seed=0, max_group=None):
+    """``adamw_flat_ex`` with one ``(lr, weight_decay)`` per parameter group: ``seg_group`` uint8 on the device names the group of every
+    segment, ``lrs`` / ``weight_decays`` are host sequences (1..8 entries) that travel by value with the launch."""
+    mode = ADAMW_MODES.get(mode, mode)
+    _need(p, BF16, "p"), _need(g, BF16, "g"), _need(m, torch.float32, "m"), _need(v, torch.float32, "v")
+    _need(seg_start, torch.int64, "seg_start"), _need(seg_active, torch.uint8, "seg_active")
+    if seg_step is not None:
+        _need(seg_step, torch.int32, "seg_step")
+    if clip_coef is not None:
+        _need(clip_coef, torch.float32, "clip_coef")
+    if lo is not None:
+        _need(lo, torch.int16, "lo")
+        if lo.numel() != p.numel():
+            raise RuntimeError(f"orv_amd.ops: `lo` holds {lo.numel()} elements, `p` {p.numel()}")
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v), ("seg_start", seg_start), ("seg_active", seg_active), ("seg_step", seg_step),
+                    ("lo", lo)):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+    if g.numel() < p.numel() or m.numel() != p.numel() or v.numel() != p.numel() or seg_start.numel() != seg_active.numel() + 1:
+        raise RuntimeError("orv_amd.ops: adamw_flat_groups buffers do not share one flat layout")
+    tab = _adamw_groups(seg_group, seg_active, lrs, weight_decays, max_group)
+    check(lib().orv_adamw_flat_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(seg_start), _p(seg_active), _p(seg_step),
+                                      seg_active.numel(), _p(seg_group), tab, float(beta1), float(beta2), float(eps), int(step),
+                                      _p(clip_coef), _p(lo), int(mode), int(seed) & 0xFFFFFFFF, _stream()), "orv_adamw_flat_groups")
+
+
+def adamw_flat_s8_groups(p, g, m8, v8, m_exp, v_exp, seg_start, seg_active, seg_group, lrs, weight_decays, beta1, beta2, eps, step,
+                         clip_coef=None, seg_step=None, lo=None, mode=0, seed=0, max_group=None, common_count=0):
+    """``adamw_flat_s8`` with one ``(lr, weight_decay)`` per parameter group (see ``adamw_flat_groups``).  ``common_count``: the
+    per-segment count most segments are at when it is not ``step`` (after a skipped step); it only spares the kernel its own bias
+    corrections, the result does not depend on it."""
+    mode = ADAMW_MODES.get(mode, mode)
+    _need(p, BF16, "p"), _need(g, BF16, "g"), _need_state8(m8, m_exp, "m8"), _need_state8(v8, v_exp, "v8")
+    _need(seg_start, torch.int64, "seg_start"), _need(seg_active, torch.uint8, "seg_active")
+    if seg_step is not None:
+        _need(seg_step, torch.int32, "seg_step")
+    if clip_coef is not None:
+        _need(clip_coef, torch.float32, "clip_coef")
+    if lo is not None:
+        _need(lo, torch.int16, "lo")
+        if lo.numel() != p.numel():
+            raise RuntimeError(f"orv_amd.ops: `lo` holds {lo.numel()} elements, `p` {p.numel()}")
+    for name, t in (("p", p), ("g", g), ("seg_start", seg_start), ("seg_active", seg_active), ("seg_step", seg_step), ("lo", lo)):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+    if g.numel() < p.numel() or m8.numel() != p.numel() or v8.numel() != p.numel() or seg_start.numel() != seg_active.numel() + 1:
+        raise RuntimeError("orv_amd.ops: adamw_flat_s8_groups buffers do not share one flat layout")
+    tab = _adamw_groups(seg_group, seg_active, lrs, weight_decays, max_group)
+    check(lib().orv_adamw_flat_s8_groups(_p(p), _p(g), _p(m8), _p(v8), _p(m_exp), _p(v_exp), p.numel(), _p(seg_start), _p(seg_active),
+                                         _p(seg_step), seg_active.numel(), _p(seg_group), tab, float(beta1), float(beta2), float(eps),
+                                         int(step), int(common_count), _p(clip_coef), _p(lo), int(mode), int(seed) & 0xFFFFFFFF,
+                                         _stream()), "orv_adamw_flat_s8_groups")
+
+
+def segment_sumsq(g, seg_start, out):
+    """``out[i]`` (fp64) = the sum of squares of the bf16 elements ``g[seg_start[i]:seg_start[i + 1]]``, one launch, in the fixed order
+    stated in ``orv_amd/csrc/optim_groups.hip``.  The caller guarantees that ``seg_start`` is ascending and ends inside ``g``."""
+    _need(g, BF16, "g"), _need(seg_start, torch.int64, "seg_start"), _need(out, torch.float64, "out")
+    if not (g.is_contiguous() and seg_start.is_contiguous() and out.is_contiguous()) or seg_start.numel() != out.numel() + 1:
+        raise RuntimeError(f"orv_amd.ops: segment_sumsq wants contiguous buffers and len(seg_start) == len(out) + 1 "
+                           f"(got {seg_start.numel()} and {out.numel()})")
+    check(lib().orv_segment_sumsq(_p(g), _p(seg_start), out.numel(), _p(out), _stream()), "orv_segment_sumsq")
+
+
+def step_guard(seg_ss, seg_group, seg_active, clip_coef, report, max_grad_norm, inv_world=1.0, skip_nonfinite=False):
+    """The device-side decisions of one optimizer step (``orv_step_guard``): global and per-group sums of ``seg_ss`` in index order, the
+    clip coefficient, and - with ``skip_nonfinite`` and a non-finite sum - a cleared ``seg_active`` and a counted skip.  ``report``: fp64
+    ``[len(GUARD_REPORT)]``, zeroed once by the caller."""
+    _need(seg_ss, torch.float64, "seg_ss"), _need(seg_group, torch.uint8, "seg_group"), _need(seg_active, torch.uint8, "seg_active")
+    _need(clip_coef, torch.float32, "clip_coef"), _need(report, torch.float64, "report")
+    n = seg_ss.numel()
+    if seg_group.numel() != n or seg_active.numel() != n or report.numel() != len(GUARD_REPORT) or clip_coef.numel() < 1:
+        raise RuntimeError(f"orv_amd.ops: step_guard wants {n} bytes in seg_group and seg_active, {len(GUARD_REPORT)} doubles in report")
+    for name, t in (("seg_ss", seg_ss), ("seg_group", seg_group), ("seg_active", seg_active), ("report", report)):
+        if not t.is_contiguous():
+            raise RuntimeError(f"orv_amd.ops: `{name}` must be contiguous")
+    check(lib().orv_step_guard(_p(seg_ss), _p(seg_group), n, float(max_grad_norm), float(inv_world), int(bool(skip_nonfinite)),
+                               _p(seg_active), _p(clip_coef), _p(report), _stream()), "orv_step_guard")
 
 
 def state8_quantize(x, q, exps, fmt, seed=0, step=0):

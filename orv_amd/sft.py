@@ -178,10 +178,15 @@ def sft_step(transformer, scheduler, optimizer, b: Batch, generator: Optional[to
     if sync:
         parts["grad_norm"] = optimizer.step(average_over=world)       # (finishes) the exchange, averages, clips, updates
         optimizer.zero_grad()
-        if ema is not None:
+        # the skip guard (FusedAdamW(skip_nonfinite=True)): a step with a non-finite gradient norm updated nothing on the device; the flag
+        # came to the host with the norm, and neither the EMA nor the schedule moves - the whole run state stays where it was
+        skipped = False
+        if getattr(optimizer, "skip_nonfinite", False):
+            skipped = parts["skipped"] = bool(optimizer.last_step_skipped)
+        if ema is not None and not skipped:
             ema.step()
         if lr_scheduler is not None:                                  # :1107 through accelerate's AcceleratedScheduler (split_batches False)
-            for _ in range(world):
+            for _ in range(0 if skipped else world):
                 lr_scheduler.step()
             parts["lr"] = lr_scheduler.get_last_lr()[0]
     return loss.detach(), parts
